@@ -16,6 +16,10 @@ torchrun rendezvous open (the GPU work happens in the framework's own
 worker actors, one per GPU, with their own RCCL process group).
 `--raw` bypasses the framework (plain DDP in the torchrun ranks) to
 measure framework overhead A/B.
+
+A plain run sets up, warms up, times `--steps` steps and prints one JSON
+result line. `--dump-outputs DIR` additionally saves what the last timed
+step computed; `--full` is reserved for secondary measurements.
 """
 from __future__ import annotations
 
@@ -44,7 +48,50 @@ def parse_args():
     p.add_argument("--raw", action="store_true",
                    help="bypass the framework: plain torchrun DDP "
                         "(for framework-overhead A/B only)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed "
+                        "step computed to DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check; "
+                        "a plain run only times the headline steps "
+                        "(currently there is nothing secondary to run)")
+    args = p.parse_args()
+    if args.dump_outputs:
+        if args.model == "ppo":
+            p.error("--dump-outputs covers the training-step models, not ppo")
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
+
+
+# ---------------------------------------------------------------------------
+# --dump-outputs: what the last timed step handed back
+# ---------------------------------------------------------------------------
+
+_DUMP_SEED = 20240531
+_DUMP_PER_TENSOR = 4096
+
+
+def dump_outputs(dump_dir, loss, model):
+    """Write the result of the last timed step as float32 .npy files:
+    `loss.npy` is the loss the step returned, `param_sample.npy` a fixed,
+    seeded sample (<= 4096 elements per tensor, in parameter order) of
+    the weights its optimizer update left behind. A few MB in total."""
+    import numpy as np
+
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "loss.npy"),
+            loss.detach().float().reshape(-1).cpu().numpy())
+    gen = torch.Generator(device="cpu").manual_seed(_DUMP_SEED)
+    parts = []
+    for p in model.parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > _DUMP_PER_TENSOR:
+            idx = torch.randint(0, flat.numel(), (_DUMP_PER_TENSOR,),
+                                generator=gen)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(dump_dir, "param_sample.npy"),
+            torch.cat(parts).numpy())
 
 
 # ---------------------------------------------------------------------------
@@ -85,6 +132,8 @@ def _timed_dist_loop(cfg, build, step_fn):
                          device="cpu" if use_cpu else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if cfg.get("dump_outputs") and ctx.get_world_rank() == 0:
+        dump_outputs(cfg["dump_outputs"], loss, state["model"])
     train.report({
         "elapsed_s": elapsed,
         "final_loss": float(loss.detach().float().cpu()),
@@ -215,6 +264,7 @@ def run_framework(args, n, use_cpu):
             "steps": args.steps,
             "warmup": args.warmup,
             "use_cpu": use_cpu,
+            "dump_outputs": args.dump_outputs,
         }
         trainer = TorchTrainer(
             loop,
@@ -405,6 +455,9 @@ def run_torchrun_paths(args, world_size, rank, use_cpu):
                          device=device if not use_cpu else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
 
     total_samples = args.steps * B * world_size
     samples_per_sec = total_samples / elapsed

@@ -10,6 +10,19 @@ import pytest
 import ray_amd as ray
 
 
+@pytest.fixture
+def gcs_sock_dir():
+    """A directory with a short path for unix sockets: sun_path holds
+    ~107 bytes, and pytest's tmp_path (base temp + user + test name)
+    can exceed that."""
+    import shutil
+    import tempfile
+
+    d = tempfile.mkdtemp(prefix="rgcs", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
 def test_object_spilling_and_restore():
     # tiny store budget forces spill of the older object, then restore
     ray.init(num_cpus=2, object_store_memory=40 * 1024 * 1024,
@@ -326,7 +339,8 @@ def test_borrower_crash_sweeps_and_frees(ray_start_regular):
     assert not rt._borrows.get(oid)
 
 
-def test_gcs_sqlite_journal_survives_hard_kill(tmp_path, monkeypatch):
+def test_gcs_sqlite_journal_survives_hard_kill(tmp_path, gcs_sock_dir,
+                                               monkeypatch):
     """Sqlite storage backend (reference: Redis-backed GCS store for
     HA): a kv_put acknowledged right before kill -9 is replayed from
     the synchronous journal — the file backend would lose anything
@@ -336,7 +350,7 @@ def test_gcs_sqlite_journal_survives_hard_kill(tmp_path, monkeypatch):
     import socket as _socket
 
     monkeypatch.setenv("RAY_AMD_GCS_STORAGE", "sqlite")
-    sock = str(tmp_path / "gcs.sock")
+    sock = os.path.join(gcs_sock_dir, "gcs.sock")
     persist = str(tmp_path / "gcs_state")
     env = dict(os.environ)
 
@@ -390,7 +404,8 @@ def test_gcs_sqlite_journal_survives_hard_kill(tmp_path, monkeypatch):
         proc.wait(5)
 
 
-def test_gcs_sqlite_journal_actor_registration(tmp_path, monkeypatch):
+def test_gcs_sqlite_journal_actor_registration(tmp_path, gcs_sock_dir,
+                                               monkeypatch):
     """Actor registrations journal synchronously too: a named actor
     registered right before kill -9 is rescheduled by the restarted
     GCS (no snapshot flush needed)."""
@@ -400,7 +415,7 @@ def test_gcs_sqlite_journal_actor_registration(tmp_path, monkeypatch):
     import socket as _socket
 
     monkeypatch.setenv("RAY_AMD_GCS_STORAGE", "sqlite")
-    sock = str(tmp_path / "gcs.sock")
+    sock = os.path.join(gcs_sock_dir, "gcs.sock")
     persist = str(tmp_path / "gcs_state")
     env = dict(os.environ)
 
