@@ -18,6 +18,7 @@
 #include "hip/fa_bwd_dq_v4.hip"
 #include "hip/fa_bwd_dkv_v5.hip"
 #include "hip/gemv.hip"
+#include "hip/paged_attn.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                       \
@@ -143,6 +144,180 @@ at::Tensor gemv(at::Tensor x, at::Tensor w) {
                      (const short*)w.data_ptr(), (const short*)x.data_ptr(),
                      (short*)y.data_ptr(), N, B, K);
   return y;
+}
+
+// ---------------- paged-KV decode attention ----------------
+
+#define CHECK_I32(x)                                                    \
+  CHECK_IN(x);                                                          \
+  TORCH_CHECK(x.scalar_type() == at::kInt, #x " must be int32")
+
+static void check_paged_cache(const at::Tensor& k_cache,
+                              const at::Tensor& v_cache, int Hkv, int D) {
+  CHECK_IN(k_cache); CHECK_IN(v_cache);
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 &&
+              v_cache.scalar_type() == at::kBFloat16,
+              "paged cache must be bf16");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(),
+              "k_cache/v_cache must both be [num_pages, Hkv, 16, D]");
+  TORCH_CHECK(k_cache.size(0) >= 1 && k_cache.size(1) == Hkv &&
+              k_cache.size(2) == PA_PAGE && k_cache.size(3) == D,
+              "paged cache must be [num_pages, Hkv, 16, D] matching q/k");
+}
+
+static void launch_paged_reduce(const at::Tensor& ws, at::Tensor& out, int B,
+                                int Hq, int D, int S) {
+  const float* ws_o = ws.data_ptr<float>();
+  const float* ws_ml = ws_o + (long long)B * Hq * S * D;
+  hipLaunchKernelGGL(paged_attn_reduce_bf16, dim3(Hq, B), dim3(D), 0,
+                     cur_stream(), ws_o, ws_ml, (short*)out.data_ptr(), Hq, S,
+                     D);
+}
+
+// Combine split partials; workspace is [B*Hq*S*(D+2)] fp32 as written
+// by paged_attn_decode (o partials, then (m, l) pairs).
+at::Tensor paged_attn_reduce(at::Tensor workspace, int64_t B, int64_t Hq,
+                             int64_t D, int64_t num_splits) {
+  CHECK_IN(workspace);
+  TORCH_CHECK(workspace.scalar_type() == at::kFloat, "workspace must be fp32");
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(B >= 1 && B <= 65535 && Hq >= 1 && Hq <= 65535 &&
+              num_splits >= 1, "paged_attn_reduce: bad B/Hq/num_splits");
+  TORCH_CHECK(workspace.numel() >= B * Hq * num_splits * (D + 2),
+              "paged_attn: workspace too small");
+  auto out = at::empty({B, Hq, D}, workspace.options().dtype(at::kBFloat16));
+  launch_paged_reduce(workspace, out, (int)B, (int)Hq, (int)D,
+                      (int)num_splits);
+  return out;
+}
+
+template <int D, int REP>
+static void launch_paged_decode(const at::Tensor& q, const at::Tensor& kc,
+                                const at::Tensor& vc, const at::Tensor& bt,
+                                const at::Tensor& sl, at::Tensor& out,
+                                float* ws_o, float* ws_ml, int S, int Hkv) {
+  int B = (int)q.size(0);
+  hipLaunchKernelGGL((paged_attn_decode_bf16<D, REP>), dim3(S, Hkv, B),
+                     dim3(256), 0, cur_stream(), (const short*)q.data_ptr(),
+                     (const short*)kc.data_ptr(), (const short*)vc.data_ptr(),
+                     bt.data_ptr<int>(), sl.data_ptr<int>(),
+                     (short*)out.data_ptr(), ws_o, ws_ml, Hkv,
+                     (int)kc.size(0), (int)bt.size(1),
+                     1.4426950408889634f / sqrtf((float)D));
+}
+
+at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
+                             at::Tensor v_cache, at::Tensor block_table,
+                             at::Tensor seq_lens, int64_t num_splits,
+                             c10::optional<at::Tensor> workspace) {
+  CHECK_IN(q);
+  CHECK_I32(block_table);
+  CHECK_I32(seq_lens);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
+  TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
+  int B = (int)q.size(0), Hq = (int)q.size(1), D = (int)q.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
+  int Hkv = (int)k_cache.size(1);
+  check_paged_cache(k_cache, v_cache, Hkv, D);
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  int rep = Hq / Hkv;
+  TORCH_CHECK(rep == 1 || rep == 2 || rep == 4 || rep == 8,
+              "paged_attn: Hq/Hkv must be 1, 2, 4 or 8");
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+              block_table.size(1) >= 1,
+              "block_table must be [B, max_pages]");
+  TORCH_CHECK(seq_lens.dim() == 1 && seq_lens.size(0) == B,
+              "seq_lens must be [B]");
+  TORCH_CHECK(B >= 1 && B <= 65535 && Hkv <= 65535,
+              "paged_attn: B and Hkv must fit a grid dimension");
+  int S = (int)num_splits;
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 1024,
+              "paged_attn: num_splits must be 1..1024");
+  auto out = at::empty({B, Hq, D}, q.options());
+  at::Tensor ws;
+  float *ws_o = nullptr, *ws_ml = nullptr;
+  if (S > 1) {
+    long long need = (long long)B * Hq * S * (D + 2);
+    if (workspace.has_value()) {
+      ws = *workspace;
+      CHECK_IN(ws);
+      TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= need,
+                  "paged_attn: workspace must be fp32 with >= B*Hq*S*(D+2) "
+                  "elements");
+    } else {
+      ws = at::empty({need}, q.options().dtype(at::kFloat));
+    }
+    ws_o = ws.data_ptr<float>();
+    ws_ml = ws_o + (long long)B * Hq * S * D;
+  }
+#define PA_LAUNCH(DD, RR)                                                   \
+  launch_paged_decode<DD, RR>(q, k_cache, v_cache, block_table, seq_lens,   \
+                              out, ws_o, ws_ml, S, Hkv)
+#define PA_REP(DD)                                                          \
+  switch (rep) {                                                            \
+    case 1: PA_LAUNCH(DD, 1); break;                                        \
+    case 2: PA_LAUNCH(DD, 2); break;                                        \
+    case 4: PA_LAUNCH(DD, 4); break;                                        \
+    default: PA_LAUNCH(DD, 8); break;                                       \
+  }
+  if (D == 64) { PA_REP(64) } else { PA_REP(128) }
+#undef PA_REP
+#undef PA_LAUNCH
+  if (S > 1) launch_paged_reduce(ws, out, B, Hq, D, S);
+  return out;
+}
+
+// q [B,Hq,D], k/v [B,Hkv,D]: contiguous or slices of a fused QKV row
+// (contiguous [H,D] tail, arbitrary 16-byte-aligned row stride).
+static long long paged_row_stride(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 3 && t.stride(2) == 1 && t.stride(1) == t.size(2),
+              name, " must be [B, H, D] with a contiguous [H, D] tail");
+  TORCH_CHECK(t.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " rows must be 16-byte aligned");
+  return (long long)t.stride(0);
+}
+
+at::Tensor rope_append_paged(at::Tensor q, at::Tensor k, at::Tensor v,
+                             at::Tensor cosT, at::Tensor sinT, at::Tensor pos,
+                             at::Tensor block_table, at::Tensor k_cache,
+                             at::Tensor v_cache) {
+  long long q_rs = paged_row_stride(q, "q");
+  long long k_rs = paged_row_stride(k, "k");
+  long long v_rs = paged_row_stride(v, "v");
+  CHECK_IN(cosT); CHECK_IN(sinT);
+  CHECK_I32(pos);
+  CHECK_I32(block_table);
+  int B = (int)q.size(0), Hq = (int)q.size(1), D = (int)q.size(2);
+  int Hkv = (int)k.size(1);
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == D &&
+              v.size(2) == D && v.size(1) == Hkv,
+              "q/k/v shapes disagree");
+  check_paged_cache(k_cache, v_cache, Hkv, D);
+  TORCH_CHECK(cosT.scalar_type() == at::kFloat &&
+              sinT.scalar_type() == at::kFloat && cosT.dim() == 2 &&
+              cosT.size(1) == D / 2 && sinT.sizes() == cosT.sizes(),
+              "cosT/sinT must be fp32 [T, D/2]");
+  TORCH_CHECK(pos.dim() == 1 && pos.size(0) == B, "pos must be [B]");
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+              block_table.size(1) >= 1,
+              "block_table must be [B, max_pages]");
+  auto q_rot = at::empty({B, Hq, D}, q.options());
+  if (B == 0) return q_rot;
+  hipLaunchKernelGGL(rope_append_paged_bf16, dim3(B), dim3(256), 0,
+                     cur_stream(), (const short*)q.data_ptr(),
+                     (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                     q_rs, k_rs, v_rs, cosT.data_ptr<float>(),
+                     sinT.data_ptr<float>(), pos.data_ptr<int>(),
+                     block_table.data_ptr<int>(), (short*)k_cache.data_ptr(),
+                     (short*)v_cache.data_ptr(), (short*)q_rot.data_ptr(), Hq,
+                     Hkv, D, (int)cosT.size(0), (int)k_cache.size(0),
+                     (int)block_table.size(1));
+  return q_rot;
 }
 
 // ---------------- AdamW ----------------
@@ -468,6 +643,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd", &flash_attn_bwd);
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("gemv", &gemv);
+  m.def("paged_attn_decode", &paged_attn_decode, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
+        py::arg("seq_lens"), py::arg("num_splits"),
+        py::arg("workspace") = py::none());
+  m.def("paged_attn_reduce", &paged_attn_reduce);
+  m.def("rope_append_paged", &rope_append_paged);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

@@ -8,4 +8,5 @@ from .engine import (  # noqa: F401
     LLMConfig,
     LLMEngine,
 )
+from .paged import PagedDecoder, PagedKVPool  # noqa: F401
 from .serving import LLMServer, build_llm_deployment, build_openai_app  # noqa: F401

@@ -30,6 +30,11 @@ class LLMConfig:
     dtype: str = "bfloat16"
     use_hip_graph: bool = True
     temperature: float = 0.0
+    # ContinuousBatchingEngine only: "contiguous" (BatchedDecoder) or
+    # "paged" (PagedDecoder over a page pool). kv_num_pages counts the
+    # reserved null page; default fits max_batch_size x max_seq_len.
+    kv_cache: str = "contiguous"
+    kv_num_pages: Optional[int] = None
 
 
 class LLMEngine:
@@ -161,8 +166,22 @@ class ContinuousBatchingEngine:
         self.model.sinT = self.model.sinT.to(self.device)
         self.max_T = min(config.max_seq_len, cfg.max_seq_len)
         self.B = max(1, config.max_batch_size)
-        self.decoder = BatchedDecoder(self.model, self.B, self.max_T,
-                                      self.device)
+        if config.kv_cache not in ("contiguous", "paged"):
+            raise ValueError(
+                f"kv_cache must be 'contiguous' or 'paged', got "
+                f"{config.kv_cache!r}")
+        self._paged = config.kv_cache == "paged"
+        if self._paged:
+            from ray_amd.llm.paged import PagedDecoder
+
+            self.decoder = PagedDecoder(self.model, self.B, self.max_T,
+                                        self.device,
+                                        num_pages=config.kv_num_pages)
+            if config.use_hip_graph and self.device.type == "cuda":
+                self.decoder.capture()
+        else:
+            self.decoder = BatchedDecoder(self.model, self.B, self.max_T,
+                                          self.device)
         self._queue: List[dict] = []          # pending requests
         self._slots: List[Optional[dict]] = [None] * self.B
         self._finished: List[dict] = []
@@ -173,6 +192,17 @@ class ContinuousBatchingEngine:
                                 device=self.device)
         self.stats = {"requests": 0, "tokens_generated": 0,
                       "decode_steps": 0}
+        self._sync_page_stats()
+
+    def _sync_page_stats(self):
+        if self._paged:
+            pool = self.decoder.pool
+            self.stats["kv_pages_total"] = pool.num_usable
+            self.stats["kv_pages_free"] = pool.num_free
+
+    def _reserve_tokens(self, prompt_len: int, max_new_tokens: int) -> int:
+        """KV rows a request can ever occupy (prompt + decode budget)."""
+        return min(prompt_len + max_new_tokens, self.max_T)
 
     def submit(self, prompt_ids: List[int], max_new_tokens: int = 32,
                temperature: Optional[float] = None) -> int:
@@ -182,6 +212,15 @@ class ContinuousBatchingEngine:
         prompt = [t % cfg.vocab_size for t in prompt_ids][
             : self.max_T - max_new_tokens - 1
         ]
+        if self._paged:
+            from ray_amd.llm.paged import pages_for
+
+            need = pages_for(self._reserve_tokens(len(prompt),
+                                                  max_new_tokens))
+            if need > self.decoder.pool.num_usable:
+                raise ValueError(
+                    f"request needs {need} KV pages but the pool holds "
+                    f"{self.decoder.pool.num_usable}; raise kv_num_pages")
         self._queue.append({
             "id": rid, "prompt": prompt,
             "max_new_tokens": max_new_tokens,
@@ -201,10 +240,21 @@ class ContinuousBatchingEngine:
         for slot in range(self.B):
             if self._slots[slot] is not None or not self._queue:
                 continue
+            if self._paged:
+                # admit only when the head request's pages fit; requests
+                # behind it may not overtake it
+                head = self._queue[0]
+                reserve = self._reserve_tokens(len(head["prompt"]),
+                                               head["max_new_tokens"])
+                if not self.decoder.can_reserve(reserve):
+                    break
             req = self._queue.pop(0)
             toks = torch.tensor(req["prompt"], device=self.device)
             with torch.no_grad():
-                logits = self.decoder.prefill_slot(slot, toks)
+                if self._paged:
+                    logits = self.decoder.prefill_slot(slot, toks, reserve)
+                else:
+                    logits = self.decoder.prefill_slot(slot, toks)
             first = self._sample(logits, req["temperature"])
             req.update({
                 "out": [first],
@@ -212,10 +262,14 @@ class ContinuousBatchingEngine:
                 "slot": slot,
             })
             self._slots[slot] = req
+        self._sync_page_stats()
 
     def _retire(self, slot: int):
         req = self._slots[slot]
         self._slots[slot] = None
+        if self._paged:
+            self.decoder.release_slot(slot)
+            self._sync_page_stats()
         self._finished.append({
             "id": req["id"], "token_ids": req["out"],
         })

@@ -340,8 +340,9 @@ class BatchedDecoder:
     """Single-token decode for a BATCH of independent sequences at
     per-slot positions — the substrate for continuous batching
     (reference: serve LLM's vLLM engine loop). Same static-buffer
-    design as GraphedDecoder but pos/mask are per-row; eager execution
-    (hipGraph capture of the batched step lands next round)."""
+    design as GraphedDecoder but pos/mask are per-row; eager execution.
+    The graph-captured batched step, over a paged cache with a fused
+    decode-attention kernel, is ray_amd.llm.paged.PagedDecoder."""
 
     def __init__(self, model: "LlamaModel", batch_size: int, max_T: int,
                  device):

@@ -543,3 +543,105 @@ def flash_attention(q, k, v, causal: bool = True, q_offset: int = 0,
         lse = r[1][:, :, :T] if pad else r[1]
         return out, lse
     return out
+
+
+# --------------------------------------------------------------------------
+# Paged-KV decode attention (serving; csrc/hip/paged_attn.hip)
+# --------------------------------------------------------------------------
+
+PAGE_SIZE = 16
+
+
+def paged_attention_ref(q, k_cache, v_cache, block_table, seq_lens):
+    """fp32 reference. q [B,Hq,D]; k_cache/v_cache
+    [num_pages,Hkv,page,D]; block_table [B,max_pages]; seq_lens [B].
+    Gathers each row's pages, slices to seq_len, GQA by
+    repeat_interleave. Rows with seq_len 0 give zeros."""
+    import math
+
+    B, Hq, D = q.shape
+    _, Hkv, page, _ = k_cache.shape
+    rep = Hq // Hkv
+    out = torch.zeros(B, Hq, D, dtype=torch.float32, device=q.device)
+    lens = seq_lens.tolist()
+    for b in range(B):
+        n = int(lens[b])
+        if n <= 0:
+            continue
+        pages = block_table[b, : (n + page - 1) // page].long()
+        # [P,Hkv,page,D] -> [Hkv, P*page, D]
+        k = k_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :n]
+        v = v_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :n]
+        kf = k.float().repeat_interleave(rep, dim=0)
+        vf = v.float().repeat_interleave(rep, dim=0)
+        s = torch.einsum("hd,htd->ht", q[b].float(), kf) / math.sqrt(D)
+        out[b] = torch.einsum("ht,htd->hd", torch.softmax(s, -1), vf)
+    return out.to(q.dtype)
+
+
+def default_num_splits(B: int, Hkv: int, max_len: int, device=None) -> int:
+    """KV splits so that B*Hkv*splits is one to two times the CU count,
+    capped at one split per 256 tokens of the longest possible row."""
+    cus = 256
+    if torch.cuda.is_available():
+        cus = torch.cuda.get_device_properties(
+            device if device is not None else 0
+        ).multi_processor_count
+    # two blocks per CU when the split count allows it: each SIMD then
+    # holds two waves, and one wave's loads hide the other's math
+    want = (2 * cus) // max(1, B * Hkv)
+    return max(1, min(want, -(-max_len // 256)))
+
+
+def paged_attention_decode(q, k_cache, v_cache, block_table, seq_lens,
+                           num_splits=None, workspace=None):
+    """Single-token attention over a paged KV cache. q [B,Hq,D] ->
+    [B,Hq,D]. num_splits=None picks a value from the block table's
+    capacity (no host sync on seq_lens); graph-capturing callers pass a
+    fixed value and may pass a static fp32 `workspace` of
+    B*Hq*num_splits*(D+2) elements."""
+    if not q.is_cuda:
+        return paged_attention_ref(q, k_cache, v_cache, block_table,
+                                   seq_lens)
+    _require_ext("paged_attention_decode")
+    if num_splits is None:
+        num_splits = default_num_splits(
+            q.shape[0], k_cache.shape[1],
+            block_table.shape[1] * k_cache.shape[2], q.device)
+    return _K.paged_attn_decode(q, k_cache, v_cache, block_table, seq_lens,
+                                int(num_splits), workspace)
+
+
+def rope_append_paged_ref(q, k, v, cosT, sinT, pos, block_table, k_cache,
+                          v_cache):
+    """Reference for rope_append_paged: rotate-halves RoPE of q/k at
+    each row's own position (fp32 tables), rotated k and raw v written
+    in place into page block_table[b, pos//page] slot pos%page; rows
+    with pos < 0 are skipped (zero q_rot). Returns q_rot [B,Hq,D]."""
+    B, Hq, D = q.shape
+    page = k_cache.shape[2]
+    q_rot = torch.zeros(B, Hq, D, dtype=q.dtype, device=q.device)
+    for b, p in enumerate(pos.tolist()):
+        if p < 0:
+            continue
+        c, s = cosT[p : p + 1], sinT[p : p + 1]
+        q_rot[b] = rope_ref(q[b].reshape(1, 1, Hq, D), c, s)[0, 0]
+        pg = int(block_table[b, p // page])
+        k_cache[pg, :, p % page] = rope_ref(
+            k[b].reshape(1, 1, -1, D), c, s)[0, 0].to(k_cache.dtype)
+        v_cache[pg, :, p % page] = v[b].to(v_cache.dtype)
+    return q_rot
+
+
+def rope_append_paged(q, k, v, cosT, sinT, pos, block_table, k_cache,
+                      v_cache):
+    """Fused decode-step RoPE + paged KV append (one launch). q
+    [B,Hq,D], k/v [B,Hkv,D] (fused-QKV slices accepted as they are),
+    pos [B] int32. Updates k_cache/v_cache in place, returns rotated
+    q."""
+    if not q.is_cuda:
+        return rope_append_paged_ref(q, k, v, cosT, sinT, pos, block_table,
+                                     k_cache, v_cache)
+    _require_ext("rope_append_paged")
+    return _K.rope_append_paged(q, k, v, cosT, sinT, pos, block_table,
+                                k_cache, v_cache)
