@@ -17,6 +17,8 @@
 #include "hip/fa_bwd_v4.hip"
 #include "hip/fa_bwd_dq_v4.hip"
 #include "hip/fa_bwd_dkv_v5.hip"
+#include "hip/fa_bwd_dkv_v6.hip"
+#include "hip/fa_bwd_dq_v5.hip"
 #include "hip/gemv.hip"
 #include "hip/paged_attn.hip"
 
@@ -530,7 +532,17 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
               "BTHD layout requires the v3/v4 backward path");
   // dq v4 (8-wave + tr16 K-gathers) measured 12.68 vs v3 13.15 ms
   // whole-bwd; the pre-tr16 v4 had regressed — tr16 flipped it
-  if (v3 && T % 256 == 0 && getenv("RAY_AMD_FA_NO_DQ_V4") == nullptr)
+  // dq v5: 64-row K/V tiles, split (issue-early / write-late) staging.
+  // RAY_AMD_FA_NO_DQ_V5 selects v4.
+  if (v3 && T % 256 == 0 && getenv("RAY_AMD_FA_NO_DQ_V4") == nullptr &&
+      getenv("RAY_AMD_FA_NO_DQ_V5") == nullptr) {
+    hipLaunchKernelGGL(fa_bwd_dq_v5_bf16, dim3(T / 256, B * Hq),
+                       dim3(512), 0, cur_stream(), (const short*)q.data_ptr(),
+                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
+                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
+                       dsum.data_ptr<float>(), (short*)dq.data_ptr(), B, Hq,
+                       Hkv, T, causal ? 1 : 0, scale, bthd);
+  } else if (v3 && T % 256 == 0 && getenv("RAY_AMD_FA_NO_DQ_V4") == nullptr)
     hipLaunchKernelGGL(fa_bwd_dq_v4_bf16, dim3(T / 256, B * Hq), dim3(512),
                        0, cur_stream(), (const short*)q.data_ptr(),
                        (const short*)k.data_ptr(), (const short*)v.data_ptr(),
@@ -557,6 +569,26 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
     // (256 kv rows) when the shape allows
     bool v4 = (T % 256 == 0) &&
               (bthd || getenv("RAY_AMD_FA_BWD_V3ONLY") == nullptr);
+    if (v4 && getenv("RAY_AMD_FA_NO_DKV5") == nullptr &&
+        getenv("RAY_AMD_FA_NO_DKV6") == nullptr) {
+      // v6: key on the MFMA lane, so P and dS feed the dV^T / dK^T
+      // products from registers; split staging; whole-row epilogue.
+      // Key block is the slow grid dimension (heaviest causal block
+      // first) unless RAY_AMD_FA_DKV6_KB_FAST asks for v5's order.
+      const int kb_slow = getenv("RAY_AMD_FA_DKV6_KB_FAST") == nullptr;
+      hipLaunchKernelGGL(fa_bwd_dkv_v6_bf16,
+                         kb_slow ? dim3(B * Hkv, T / 256)
+                                 : dim3(T / 256, B * Hkv),
+                         dim3(512), 0, cur_stream(),
+                         (const short*)q.data_ptr(),
+                         (const short*)k.data_ptr(),
+                         (const short*)v.data_ptr(),
+                         (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
+                         dsum.data_ptr<float>(), (short*)dk.data_ptr(),
+                         (short*)dv.data_ptr(), B, Hq, Hkv, T,
+                         causal ? 1 : 0, scale, bthd, kb_slow);
+      return {dq, dk, dv};
+    }
     if (v4 && getenv("RAY_AMD_FA_NO_DKV5") == nullptr) {
       // v5: fused dK+dV — S and dP computed once per tile, half the
       // Q/dO staging; V comes from LDS to stay at 2 waves/SIMD
