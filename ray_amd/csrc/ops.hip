@@ -21,6 +21,7 @@
 #include "hip/fa_bwd_dq_v5.hip"
 #include "hip/gemv.hip"
 #include "hip/paged_attn.hip"
+#include "hip/gemm_wgrad.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                       \
@@ -320,6 +321,84 @@ at::Tensor rope_append_paged(at::Tensor q, at::Tensor k, at::Tensor v,
                      Hkv, D, (int)cosT.size(0), (int)k_cache.size(0),
                      (int)block_table.size(1));
   return q_rot;
+}
+
+// ---------------- weight-gradient GEMM ----------------
+
+// [rows, cols] bf16, unit column stride, 16-byte-aligned rows (a column
+// slice of a wider tensor qualifies); returns the row stride in elements
+static long long wgrad_operand(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1),
+              name, " must be 2-D with unit column stride");
+  TORCH_CHECK(t.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " rows must be 16-byte aligned");
+  TORCH_CHECK(t.size(1) % 256 == 0 && t.size(1) >= 256, name,
+              ": columns must be a multiple of 256");
+  return (long long)t.stride(0);
+}
+
+static void launch_wgrad(const at::Tensor& dy0, const at::Tensor& dy1,
+                         const at::Tensor& x, at::Tensor& out0,
+                         at::Tensor& out1, int problems) {
+  const long long ldy = wgrad_operand(dy0, "dy");
+  const long long ldx = wgrad_operand(x, "x");
+  const long long ldo = wgrad_operand(out0, "out");
+  const long long M = dy0.size(0), N = dy0.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == M && M >= 128 && M % 128 == 0,
+              "gemm_wgrad: dy and x need the same number of rows, a "
+              "multiple of 128");
+  TORCH_CHECK(out0.size(0) == N && out0.size(1) == K,
+              "gemm_wgrad: out must be [N, K]");
+  TORCH_CHECK(ldy * 64 < (1ll << 30) && ldx * 64 < (1ll << 30),
+              "gemm_wgrad: row stride too large");
+  if (problems == 2) {
+    TORCH_CHECK(wgrad_operand(dy1, "dy1") == ldy && dy1.size(0) == M &&
+                    dy1.size(1) == N,
+                "gemm_wgrad: grouped dy operands must match");
+    TORCH_CHECK(wgrad_operand(out1, "out1") == ldo && out1.size(0) == N &&
+                    out1.size(1) == K,
+                "gemm_wgrad: grouped outputs must match");
+  }
+  const int nt0 = (int)(N / 256), KT = (int)(K / 256);
+  const int NT = nt0 * problems;
+  TORCH_CHECK((long long)NT * KT < (1ll << 31), "gemm_wgrad: grid too large");
+#define WGRAD_LAUNCH(ST)                                                     \
+  hipLaunchKernelGGL(gemm_wgrad_bf16<ST>, dim3((unsigned)(NT * KT)),         \
+                     dim3(512), 0, cur_stream(),                             \
+                     (const short*)dy0.data_ptr(),                           \
+                     (const short*)dy1.data_ptr(),                           \
+                     (const short*)x.data_ptr(), (short*)out0.data_ptr(),    \
+                     (short*)out1.data_ptr(), (int)M, ldy, ldx, ldo, NT,     \
+                     nt0, KT)
+  // read per call, like the RAY_AMD_FA_* switches
+  if (getenv("RAY_AMD_WGRAD_NO_STAGGER") != nullptr) {
+    WGRAD_LAUNCH(false);
+  } else {
+    WGRAD_LAUNCH(true);
+  }
+#undef WGRAD_LAUNCH
+}
+
+// dW[N,K] = dy[M,N]^T · x[M,K]; `out` may be a view with a larger row stride
+at::Tensor gemm_wgrad(at::Tensor dy, at::Tensor x,
+                      c10::optional<at::Tensor> out) {
+  at::Tensor o = out.has_value()
+                     ? *out
+                     : at::empty({dy.size(1), x.size(1)}, dy.options());
+  launch_wgrad(dy, dy, x, o, o, 1);
+  return o;
+}
+
+// two problems that share x (the MLP's gate and up weights) in one grid
+std::vector<at::Tensor> gemm_wgrad_grouped(at::Tensor dy0, at::Tensor dy1,
+                                           at::Tensor x) {
+  auto o0 = at::empty({dy0.size(1), x.size(1)}, dy0.options());
+  auto o1 = at::empty_like(o0);
+  launch_wgrad(dy0, dy1, x, o0, o1, 2);
+  return {o0, o1};
 }
 
 // ---------------- AdamW ----------------
@@ -675,6 +754,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd", &flash_attn_bwd);
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("gemv", &gemv);
+  m.def("gemm_wgrad", &gemm_wgrad, py::arg("dy"), py::arg("x"),
+        py::arg("out") = py::none());
+  m.def("gemm_wgrad_grouped", &gemm_wgrad_grouped);
   m.def("paged_attn_decode", &paged_attn_decode, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
         py::arg("seq_lens"), py::arg("num_splits"),

@@ -64,17 +64,17 @@ class Attention(nn.Module):
         qd = cfg.num_heads * self.head_dim
         kvd = cfg.num_kv_heads * self.head_dim
         if self._fused_qkv:
-            self.qkv_proj = nn.Linear(
+            self.qkv_proj = ops.Linear(
                 cfg.hidden_size, qd + 2 * kvd, bias=False, dtype=dtype
             )
         else:
-            self.q_proj = nn.Linear(
+            self.q_proj = ops.Linear(
                 cfg.hidden_size, qd, bias=False, dtype=dtype)
-            self.k_proj = nn.Linear(
+            self.k_proj = ops.Linear(
                 cfg.hidden_size, kvd, bias=False, dtype=dtype)
-            self.v_proj = nn.Linear(
+            self.v_proj = ops.Linear(
                 cfg.hidden_size, kvd, bias=False, dtype=dtype)
-        self.o_proj = nn.Linear(
+        self.o_proj = ops.Linear(
             cfg.num_heads * self.head_dim, cfg.hidden_size, bias=False, dtype=dtype
         )
 
@@ -140,18 +140,20 @@ class Attention(nn.Module):
 class MLP(nn.Module):
     def __init__(self, cfg: LlamaConfig, dtype=torch.bfloat16):
         super().__init__()
-        self.gate_proj = nn.Linear(
+        self.gate_proj = ops.Linear(
             cfg.hidden_size, cfg.intermediate_size, bias=False, dtype=dtype
         )
-        self.up_proj = nn.Linear(
+        self.up_proj = ops.Linear(
             cfg.hidden_size, cfg.intermediate_size, bias=False, dtype=dtype
         )
-        self.down_proj = nn.Linear(
+        self.down_proj = ops.Linear(
             cfg.intermediate_size, cfg.hidden_size, bias=False, dtype=dtype
         )
 
     def forward(self, x):
-        return self.down_proj(ops.swiglu(self.gate_proj(x), self.up_proj(x)))
+        gate, up = ops.swiglu_mlp_in(
+            x, self.gate_proj.weight, self.up_proj.weight)
+        return self.down_proj(ops.swiglu(gate, up))
 
 
 class Block(nn.Module):
@@ -177,7 +179,7 @@ class LlamaModel(nn.Module):
         self.embed = nn.Embedding(cfg.vocab_size, cfg.hidden_size, dtype=dtype)
         self.layers = nn.ModuleList(Block(cfg, dtype) for _ in range(cfg.num_layers))
         self.final_norm = ops.RMSNorm(cfg.hidden_size, cfg.rms_eps, dtype)
-        self.lm_head = nn.Linear(
+        self.lm_head = ops.Linear(
             cfg.hidden_size, cfg.vocab_size, bias=False, dtype=dtype
         )
         if cfg.tie_embeddings:

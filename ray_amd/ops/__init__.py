@@ -7,6 +7,8 @@ than silently falling back to eager torch.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 try:
@@ -182,6 +184,180 @@ def linear_sb(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
         y = _K.gemv(x.reshape(rows, K).contiguous(), weight)
         return y.view(*x.shape[:-1], weight.shape[0])
     return torch.nn.functional.linear(x, weight)
+
+
+# --------------------------------------------------------------------------
+# Linear with a hand-written weight-gradient GEMM (csrc/hip/gemm_wgrad.hip)
+# --------------------------------------------------------------------------
+
+WGRAD_M_GRANULE = 128  # tokens: the kernel's loop handles two 64-token tiles
+
+# (N, K, problems) -> use gemm_wgrad for dW[N,K] = dy^T x. A shape enters
+# only if the kernel's slowest repetition beat torch's fastest in
+# tools/gemm_wgrad_bench.py at M = 32768 (times in the comments, ms,
+# kernel median / torch median). Shapes not listed go to torch.
+_WGRAD_TABLE: dict = {
+    (14336, 4096, 1): True,   # gate / up alone: 3.160 / 3.755
+    (4096, 14336, 1): True,   # down:            3.105 / 3.767
+    (14336, 4096, 2): True,   # gate + up:       6.013 / 7.544
+    (4096, 4096, 1): True,    # o_proj:          0.820 / 0.933
+    (128256, 4096, 1): True,  # lm_head:        29.159 / 30.042
+    # qkv (6144, 4096): 1.410 / 1.414, slowest 1.431 against torch's
+    # fastest 1.405: stays with torch (384 blocks = 1.5 waves of 256 CUs)
+}
+
+# test hook: send every qualifying shape to the kernel
+_WGRAD_FORCE = False
+
+
+def _wgrad_switch_on() -> bool:
+    return not os.environ.get("RAY_AMD_NO_WGRAD_GEMM")
+
+
+def _wgrad_listed(N: int, K: int, problems: int = 1) -> bool:
+    if N % 256 or K % 256:
+        return False
+    return _WGRAD_FORCE or (N, K, problems) in _WGRAD_TABLE
+
+
+def _wgrad_operand_ok(t: torch.Tensor) -> bool:
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2
+            and t.stride(1) == 1 and t.stride(0) % 8 == 0
+            and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0
+            and t.shape[1] % 256 == 0 and t.shape[1] > 0
+            and t.stride(0) * 64 < 2 ** 30)
+
+
+def _wgrad_rows_ok(M: int) -> bool:
+    return M >= WGRAD_M_GRANULE and M % WGRAD_M_GRANULE == 0
+
+
+def gemm_wgrad(dy: torch.Tensor, x: torch.Tensor, out=None) -> torch.Tensor:
+    """dW[N,K] = dy[M,N]^T @ x[M,K] with the HIP kernel; raises when the
+    operands do not qualify (callers that want a fallback use `_wgrad`)."""
+    _require_ext("gemm_wgrad")
+    if not (_wgrad_operand_ok(dy) and _wgrad_operand_ok(x)
+            and dy.shape[0] == x.shape[0] and _wgrad_rows_ok(dy.shape[0])):
+        raise ValueError(
+            "gemm_wgrad: needs bf16 GPU operands [M,N], [M,K] with M % 128 "
+            "== 0, N % 256 == 0, K % 256 == 0 and 16-byte-aligned rows")
+    if out is not None and not (_wgrad_operand_ok(out) and tuple(out.shape)
+                                == (dy.shape[1], x.shape[1])):
+        raise ValueError("gemm_wgrad: out must be a bf16 [N,K] GPU tensor "
+                         "with 16-byte-aligned rows")
+    return _K.gemm_wgrad(dy, x, out)
+
+
+def gemm_wgrad_grouped(dy0: torch.Tensor, dy1: torch.Tensor,
+                       x: torch.Tensor):
+    """Two weight gradients that share x, one launch."""
+    _require_ext("gemm_wgrad")
+    if not (_wgrad_operand_ok(dy0) and _wgrad_operand_ok(dy1)
+            and _wgrad_operand_ok(x) and dy0.shape == dy1.shape
+            and dy0.stride(0) == dy1.stride(0)
+            and dy0.shape[0] == x.shape[0] and _wgrad_rows_ok(x.shape[0])):
+        raise ValueError("gemm_wgrad_grouped: operands do not qualify")
+    o0, o1 = _K.gemm_wgrad_grouped(dy0, dy1, x)
+    return o0, o1
+
+
+def _wgrad_use_kernel(dy2, x2, problems=1) -> bool:
+    return (_K is not None and _wgrad_switch_on()
+            and _wgrad_listed(dy2.shape[1], x2.shape[1], problems)
+            and _wgrad_operand_ok(dy2) and _wgrad_operand_ok(x2)
+            and _wgrad_rows_ok(dy2.shape[0]))
+
+
+def _wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
+    if _wgrad_use_kernel(dy2, x2):
+        return _K.gemm_wgrad(dy2, x2, None)
+    return dy2.t() @ x2
+
+
+class _LinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        return torch.nn.functional.linear(x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = dy @ weight
+        if ctx.needs_input_grad[1]:
+            dw = _wgrad(dy.reshape(-1, dy.shape[-1]),
+                        x.reshape(-1, x.shape[-1]))
+        return dx, dw
+
+
+def _linear_custom(x, weight, bias=None) -> bool:
+    return (bias is None and x.is_cuda and weight.is_cuda
+            and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+            and weight.dim() == 2 and torch.is_grad_enabled()
+            and _wgrad_switch_on())
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch.Tensor:
+    """F.linear whose weight gradient runs on gemm_wgrad for the shapes
+    listed in _WGRAD_TABLE. Everything else (CPU, non-bf16, bias, no
+    grad, RAY_AMD_NO_WGRAD_GEMM=1, unlisted shapes) is plain F.linear."""
+    if _linear_custom(x, weight, bias) and _wgrad_listed(*weight.shape):
+        return _LinearFn.apply(x, weight)
+    return torch.nn.functional.linear(x, weight, bias)
+
+
+class Linear(torch.nn.Linear):
+    """nn.Linear (same parameters, same state_dict) routed through
+    `ops.linear`."""
+
+    def forward(self, x):
+        return linear(x, self.weight, self.bias)
+
+
+class _SwigluMlpIn(torch.autograd.Function):
+    """gate = x W_gate^T, up = x W_up^T. Backward: one grouped weight
+    gradient launch (both share x). dx is the sum of the two dgrad GEMMs,
+    each rounded to bf16, exactly what autograd computes for two linears
+    (accumulating inside the second GEMM rounds once less; see
+    PERFORMANCE.md for why that is not done)."""
+
+    @staticmethod
+    def forward(ctx, x, w_gate, w_up):
+        ctx.save_for_backward(x, w_gate, w_up)
+        return (torch.nn.functional.linear(x, w_gate),
+                torch.nn.functional.linear(x, w_up))
+
+    @staticmethod
+    def backward(ctx, d_gate, d_up):
+        x, w_gate, w_up = ctx.saved_tensors
+        dg2 = d_gate.reshape(-1, d_gate.shape[-1])
+        du2 = d_up.reshape(-1, d_up.shape[-1])
+        x2 = x.reshape(-1, x.shape[-1])
+        dx = dwg = dwu = None
+        if ctx.needs_input_grad[0]:
+            dx = (dg2 @ w_gate + du2 @ w_up).view(x.shape)
+        need_g, need_u = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if (need_g and need_u and dg2.stride() == du2.stride()
+                and _wgrad_use_kernel(dg2, x2, 2)
+                and _wgrad_operand_ok(du2)):
+            dwg, dwu = _K.gemm_wgrad_grouped(dg2, du2, x2)
+        else:
+            if need_g:
+                dwg = _wgrad(dg2, x2)
+            if need_u:
+                dwu = _wgrad(du2, x2)
+        return dx, dwg, dwu
+
+
+def swiglu_mlp_in(x: torch.Tensor, w_gate: torch.Tensor,
+                  w_up: torch.Tensor):
+    """The two input projections of a SwiGLU MLP -> (gate, up)."""
+    if (_linear_custom(x, w_gate) and _linear_custom(x, w_up)
+            and w_gate.shape == w_up.shape):
+        return _SwigluMlpIn.apply(x, w_gate, w_up)
+    return linear(x, w_gate), linear(x, w_up)
 
 
 # --------------------------------------------------------------------------

@@ -6,7 +6,7 @@ import sqlite3
 import sys
 
 OURS = ("fa_bwd", "flash_attn", "adamw", "swiglu", "rope_", "rmsnorm",
-        "fused_ce", "cross_entropy", "gae_", "vtrace", "nhwc")
+        "fused_ce", "cross_entropy", "gae_", "vtrace", "nhwc", "gemm_wgrad")
 
 
 def main(path: str, top: int = 30):
