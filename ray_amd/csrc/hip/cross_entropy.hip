@@ -21,7 +21,9 @@ extern "C" __global__ __launch_bounds__(256) void ce_fwd_bf16(
   float mx = -INFINITY;
   int base = threadIdx.x * 8;
   int stride = blockDim.x * 8;
-  int V8 = (V / 8) * 8;
+  // Rows start at row*V elements: 16-byte aligned for every row only when
+  // V % 8 == 0. Any other V goes through the scalar loop whole.
+  int V8 = (V % 8 == 0) ? V : 0;
   for (int i = base; i < V8; i += stride) {
     short8 v = *reinterpret_cast<const short8*>(lr + i);
 #pragma unroll
@@ -64,7 +66,9 @@ extern "C" __global__ __launch_bounds__(256) void ce_bwd_bf16(
   float lse = row_lse[row];
   int base = threadIdx.x * 8;
   int stride = blockDim.x * 8;
-  int V8 = (V / 8) * 8;
+  // Rows start at row*V elements: 16-byte aligned for every row only when
+  // V % 8 == 0. Any other V goes through the scalar loop whole.
+  int V8 = (V % 8 == 0) ? V : 0;
   for (int i = base; i < V8; i += stride) {
     short8 v = *reinterpret_cast<const short8*>(lr + i);
     short8 o;

@@ -38,12 +38,28 @@ static inline int grid_for(long long n, int block = 256, int cap = 2048) {
 
 // ---------------- RMSNorm ----------------
 
+// The kernels read x, w and dy as raw bf16 with 16-byte loads: another
+// dtype would be reinterpreted bit for bit, so it is refused here.
+#define CHECK_RMS_BF16(t)                                               \
+  CHECK_IN(t);                                                          \
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16,                         \
+              "rmsnorm: " #t " must be bf16, got ", t.scalar_type());   \
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,      \
+              "rmsnorm: " #t " must be 16-byte aligned")
+
+static int rmsnorm_check_hw(const at::Tensor& x, const at::Tensor& w) {
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "rmsnorm: x must be [..., H]");
+  TORCH_CHECK(x.size(-1) % 8 == 0 && x.size(-1) < (1ll << 31),
+              "rmsnorm: H must be a multiple of 8");
+  TORCH_CHECK(w.dim() == 1 && w.size(0) == x.size(-1),
+              "rmsnorm: w must be [H]");
+  return (int)x.size(-1);
+}
+
 std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
-  CHECK_IN(x);
-  CHECK_IN(w);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "x must be bf16");
-  int H = (int)x.size(-1);
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  CHECK_RMS_BF16(x);
+  CHECK_RMS_BF16(w);
+  int H = rmsnorm_check_hw(x, w);
   long long N = x.numel() / H;
   auto y = at::empty_like(x);
   auto inv = at::empty({N}, x.options().dtype(at::kFloat));
@@ -56,9 +72,12 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
 
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                                     at::Tensor inv) {
-  CHECK_IN(dy); CHECK_IN(x); CHECK_IN(w); CHECK_IN(inv);
-  int H = (int)x.size(-1);
+  CHECK_RMS_BF16(dy); CHECK_RMS_BF16(x); CHECK_RMS_BF16(w); CHECK_IN(inv);
+  int H = rmsnorm_check_hw(x, w);
   long long N = x.numel() / H;
+  TORCH_CHECK(dy.sizes() == x.sizes(), "rmsnorm: dy must have x's shape");
+  TORCH_CHECK(inv.scalar_type() == at::kFloat && inv.numel() == N,
+              "rmsnorm: inv must be fp32 [N]");
   auto dx = at::empty_like(x);
   auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
   hipLaunchKernelGGL(rmsnorm_bwd_dx_bf16, dim3((unsigned)N), dim3(256), 0,
@@ -482,10 +501,23 @@ at::Tensor img_normalize(at::Tensor in, at::Tensor mean, at::Tensor inv_std) {
 
 // ---------------- cross entropy ----------------
 
-std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
+static void ce_check(const at::Tensor& logits, const at::Tensor& target) {
   CHECK_IN(logits); CHECK_IN(target);
-  TORCH_CHECK(logits.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(target.scalar_type() == at::kInt);
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16, "ce: logits must be bf16");
+  TORCH_CHECK(target.scalar_type() == at::kInt, "ce: target must be int32");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 &&
+              logits.size(1) < (1ll << 31), "ce: logits must be [N, V]");
+  TORCH_CHECK(target.dim() == 1 && target.size(0) == logits.size(0),
+              "ce: target must be [N]");
+  // the kernels use 16-byte loads only when V % 8 == 0; then every row
+  // is aligned exactly when the base is
+  TORCH_CHECK(logits.size(1) % 8 != 0 ||
+              reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "ce: logits must be 16-byte aligned");
+}
+
+std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
+  ce_check(logits, target);
   long long N = logits.size(0);
   int V = (int)logits.size(1);
   auto loss = at::empty({N}, logits.options().dtype(at::kFloat));
@@ -500,8 +532,12 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor target) {
 
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor mx,
                   at::Tensor lse, at::Tensor dloss) {
-  CHECK_IN(logits); CHECK_IN(target); CHECK_IN(dloss);
+  ce_check(logits, target);
+  CHECK_IN(mx); CHECK_IN(lse); CHECK_IN(dloss);
   long long N = logits.size(0);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == N &&
+              dloss.scalar_type() == at::kFloat && dloss.numel() == N,
+              "ce: lse and dloss must be fp32 [N]");
   int V = (int)logits.size(1);
   auto dl = at::empty_like(logits);
   hipLaunchKernelGGL(ce_bwd_bf16, dim3((unsigned)N), dim3(256), 0,

@@ -43,7 +43,10 @@ class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, eps):
         _require_ext("rmsnorm")
-        y, inv = _K.rmsnorm_fwd(x.contiguous(), w.contiguous(), eps)
+        # save what the kernel read: backward reads the same buffers
+        x = x.contiguous()
+        w = w.contiguous()
+        y, inv = _K.rmsnorm_fwd(x, w, eps)
         ctx.save_for_backward(x, w, inv)
         return y
 
@@ -391,7 +394,13 @@ class _FusedCE(torch.autograd.Function):
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor):
-    """Mean CE over rows where target != -100. logits [N, V] bf16."""
+    """Mean CE over rows where target != -100. logits [N, V] bf16.
+
+    Every negative target counts as ignored; an all-ignored batch gives
+    loss 0 and zero gradient (the row count is clamped to 1). A target
+    >= V is not checked on the GPU: the kernel reads logits[row, target]
+    out of bounds. Guarding it needs a host sync, so the caller must
+    pass targets in [0, V) or negative."""
     if not logits.is_cuda:
         return cross_entropy_ref(logits, target)
     return _FusedCE.apply(logits, target)
