@@ -1,7 +1,7 @@
 // fa_bwd dkv v6: fused dK+dV with the KEY on the MFMA lane.
 //
-// v5 computed S^T = K·Q^T (query on the lane), so the dV and dK products,
-// which sum over the query index, needed P and dS transposed: 2x16
+// With S^T = K·Q^T (query on the lane, as in fa_bwd_v3.hip) the dV and dK
+// products, which sum over the query index, need P and dS transposed: 2x16
 // two-byte LDS writes, two full waitcnt drains and 4 reads per 32x32 tile.
 // v6 computes S = Q·K^T and dP = dO·V^T (A = Q / dO rows from LDS, B = the
 // K fragment in registers / V rows from LDS). The accumulators then have
@@ -31,20 +31,19 @@
 // LDS: V 64K + q/dO double buffers 64K + row constants 1K = 129 KB. The
 // epilogue transposes dK^T/dV^T through the same memory and stores whole
 // 256-byte rows.
-#include "common.h"
+#include "fa_bwd_frag.h"
 #include "fa_bwd_lds_layout.h"
-// FB3_* and fb3_* come from fa_bwd_v3.hip, as for the v4/v5 kernels.
 
 #define FB6_EP_STRIDE 136  // epilogue row stride in bf16 (256 B + 16 B pad)
 
-// kb_slow != 0: grid is (B*Hkv, T/256), so key block 0, the heaviest under
-// the causal mask, is dispatched first; otherwise (T/256, B*Hkv) as v5.
+// Grid (B*Hkv, T/256): the key block is the slow dimension, so key block 0,
+// the heaviest under the causal mask, is dispatched first.
 extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ Dsum,
     short* __restrict__ dK, short* __restrict__ dV, int B, int Hq,
-    int Hkv, int T, int causal, float scale, int bthd, int kb_slow) {
+    int Hkv, int T, int causal, float scale, int bthd) {
   __shared__ __attribute__((aligned(16))) short smem[65536 + 512];
   // q and dO first: every tile read is then base + immediate (< 64 KB)
   short* const q_lds = smem;                  // [2][64][128]
@@ -53,8 +52,8 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
   float* const lse_lds = reinterpret_cast<float*>(smem + 65536);  // [2][64]
   float* const dsum_lds = lse_lds + 128;                          // [2][64]
 
-  const int kb = kb_slow ? blockIdx.y : blockIdx.x;
-  const int bh = kb_slow ? blockIdx.x : blockIdx.y;
+  const int kb = blockIdx.y;
+  const int bh = blockIdx.x;
   const int k0 = kb * 256;
   const int b = bh / Hkv;
   const int hkv = bh % Hkv;

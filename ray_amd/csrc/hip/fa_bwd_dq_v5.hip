@@ -1,21 +1,19 @@
-// dq v5: dq v4 (8 waves x 32 q rows, Q/dO register-resident) with
-//  - 64-row K/V tiles, double buffered: 48 MFMAs per wave per barrier
-//    (v4: 32 rows, 24 MFMAs);
+// dq v5: grid (T/256, B*Hq), 8 waves x 32 q rows, Q/dO register-resident,
+//  - 64-row K/V tiles, double buffered: 48 MFMAs per wave per barrier;
 //  - split staging: the global loads of tile t+1 are issued before tile
 //    t's MFMAs and written to the other buffer after them, before the
-//    tile's one barrier (v4 loaded and stored in one statement, so every
-//    wave sat through the load latency at the top of each tile);
+//    tile's one barrier (loading and storing in one statement makes every
+//    wave sit through the load latency at the top of each tile);
 //  - -LSE/scale and -delta as the initial accumulators of the S and dP
 //    chains (lane constants here: the query is on the lane);
-//  - v4's cvt_pk + permlane32_swap exchange of dS is kept: feeding the
-//    packed registers to the MFMA directly (permuted k order) measured
-//    slower, see PERFORMANCE.md;
+//  - dS is exchanged with cvt_pk + permlane32_swap: feeding the packed
+//    registers to the MFMA directly (permuted k order) measured slower,
+//    see PERFORMANCE.md;
 //  - the fb6_off LDS image (conflict-free row and transposed reads, two
 //    address registers per kind of read).
 // dQ[q][d] += sum_k dS^T[k][q] K[k][d]
-#include "common.h"
+#include "fa_bwd_frag.h"
 #include "fa_bwd_lds_layout.h"
-// FB3_* and fb3_* come from fa_bwd_v3.hip, as for the v4/v5 kernels.
 
 #define FB5_KT 64  // K/V rows per staged tile
 

@@ -4,24 +4,22 @@
 // double-buffered LDS tiles with the async-STAGE split (next tile's
 // global loads issue before this tile's compute), XOR-swizzled
 // ds_read_b128 on every row-read path, one __syncthreads per 64-q
-// tile (v2 paid two per 32-q tile). The GQA head loop and q-tile loop
+// tile. The GQA head loop and q-tile loop
 // are flattened into one iteration space so the software pipeline
 // runs across head boundaries.
 //
-// Math identical to fa_bwd.hip v2 (same swapped-operand S'=K·Q^T
-// structure, P^T via per-wave LDS scratch transpose, no atomics).
-#include "common.h"
-
-#define FB3_D 128
-#define FB3_QT 64           // q rows per staged tile (2 sub-tiles of 32)
-
-typedef __attribute__((ext_vector_type(8))) __bf16 fb3_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float fb3_f32x16;
-
-DEV_INLINE fb3_bf16x8 fb3_ld8(const short* p) {
-  short8 s = *reinterpret_cast<const short8*>(p);
-  return __builtin_bit_cast(fb3_bf16x8, s);
-}
+// Math (FA2-style split, Dao 2023 §3, no atomics): S' = K·Q^T on
+// mfma_f32_32x32x16_bf16 puts the softmax row (a fixed q) in ONE lane
+// column, so P^T = exp(S'·s − lse[q]) and dS̃^T = P^T ⊙ (dP^T − D[q])·s
+// are register-local elementwise ops; dP^T = V·dO^T has the same shape.
+// dV += P^T·dO and dK += dS̃^T·Q need a true 32x32 lane transpose, done
+// through a per-wave padded LDS scratch tile.
+//
+// Layout cheatsheet (fa_probe32-verified, 32x32x16):
+//   A (32x16) row-major: lane l holds A[l&31][8*(l>>5)+i]
+//   B (16x32):           lane l holds B[8*(l>>5)+i][l&31]
+//   C:                   col=lane&31, row=(r&3)+8*(r>>2)+4*(l>>5)
+#include "fa_bwd_frag.h"
 
 // ---------------------------------------------------------------------
 // dV: grid (T/128, B*Hkv); 4 waves x 32 kv rows; K in registers,
@@ -139,7 +137,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
         }
       }
       // C layout: col = lane&31 = q (this lane's loaded q row),
-      // rows = this wave's k (same as v2)
+      // rows = this wave's k
       const int gq = qts + (lane & 31);
       const float lse_q = lse_lds[cur][32 * qt + (lane & 31)];
       const bool full_tile = !causal || (k0 + 32 * wave + 31 <= qts);
@@ -356,7 +354,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
 // ---------------------------------------------------------------------
 // dQ v3: grid (T/128, B*Hq), 4 waves x 32 q rows; 32-row K/V tiles
 // double-buffered with direct global->LDS staging (one barrier per
-// tile, v2 paid two), XOR-swizzled row reads, cvt_pk+permlane dS
+// tile), XOR-swizzled row reads, cvt_pk+permlane dS
 // exchange.  dQ[q][d] += sum_k dS^T[k][q] K[k][d]
 // ---------------------------------------------------------------------
 

@@ -8,17 +8,17 @@
 #include "hip/elementwise.hip"
 #include "hip/rl_scans.hip"
 #include "hip/cross_entropy.hip"
-// Retired ladder rungs (flash_attn.hip v1-v4) stay in the tree as the
-// evidence trail but are no longer compiled into the shipped binary.
+// Flash attention has two paths, chosen from the shape alone:
+//   T % 256 == 0: 256-row kernels (fwd v6, dq v5, dkv v6), which read
+//                 contiguous BHTD or BTHD-view tensors;
+//   otherwise:    128-row kernels (fwd v5, dq/dv/dk v3), contiguous BHTD.
+// Each file below compiles on its own.
 #include "hip/flash_attn_v5.hip"
 #include "hip/flash_attn_v6.hip"
-#include "hip/fa_bwd.hip"
+#include "hip/fa_bwd_prep.hip"
 #include "hip/fa_bwd_v3.hip"
-#include "hip/fa_bwd_v4.hip"
-#include "hip/fa_bwd_dq_v4.hip"
-#include "hip/fa_bwd_dkv_v5.hip"
-#include "hip/fa_bwd_dkv_v6.hip"
 #include "hip/fa_bwd_dq_v5.hip"
+#include "hip/fa_bwd_dkv_v6.hip"
 #include "hip/gemv.hip"
 #include "hip/paged_attn.hip"
 #include "hip/gemm_wgrad.hip"
@@ -392,7 +392,7 @@ static void launch_wgrad(const at::Tensor& dy0, const at::Tensor& dy1,
                      (const short*)x.data_ptr(), (short*)out0.data_ptr(),    \
                      (short*)out1.data_ptr(), (int)M, ldy, ldx, ldo, NT,     \
                      nt0, KT)
-  // read per call, like the RAY_AMD_FA_* switches
+  // read on every call, so one process can measure both variants
   if (getenv("RAY_AMD_WGRAD_NO_STAGGER") != nullptr) {
     WGRAD_LAUNCH(false);
   } else {
@@ -576,7 +576,8 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
   int Hkv = (int)k.size(1), Tk = (int)k.size(2);
   TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   TORCH_CHECK(!bthd || T % 256 == 0,
-              "BTHD layout needs the v6 kernel (T % 256 == 0)");
+              "BTHD-view layout needs T % 256 == 0: only the 256-row "
+              "kernel reads it");
   // O matches q's layout so the model's out.transpose().reshape stays
   // a free view
   auto o = bthd
@@ -590,19 +591,20 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
     lse_ptr = lse.data_ptr<float>();
   }
   float scale = 1.0f / sqrtf((float)q.size(3));
-  if (!bthd && (getenv("RAY_AMD_FA_V5") != nullptr || T % 256 != 0))
-    hipLaunchKernelGGL(flash_attn_fwd_v5_bf16, dim3(T / 128, B * Hq),
-                       dim3(256), 0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (short*)o.data_ptr(), lse_ptr, B, Hq, Hkv, T, Tk,
-                       causal ? 1 : 0, (int)q_offset, scale);
-  else
-    // v6 (default): 8-wave dbuf/async-stage/swizzled structure
+  const short* qp = (const short*)q.data_ptr();
+  const short* kp = (const short*)k.data_ptr();
+  const short* vp = (const short*)v.data_ptr();
+  short* op = (short*)o.data_ptr();
+  const int c = causal ? 1 : 0, qo = (int)q_offset;
+  if (T % 256 == 0)
+    // 256 query rows per block: 8-wave dbuf/async-stage/swizzled structure
     hipLaunchKernelGGL(flash_attn_fwd_v6_bf16, dim3(T / 256, B * Hq),
-                       dim3(512), 0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (short*)o.data_ptr(), lse_ptr, B, Hq, Hkv, T, Tk,
-                       causal ? 1 : 0, (int)q_offset, scale, bthd);
+                       dim3(512), 0, cur_stream(), qp, kp, vp, op, lse_ptr,
+                       B, Hq, Hkv, T, Tk, c, qo, scale, bthd);
+  else
+    hipLaunchKernelGGL(flash_attn_fwd_v5_bf16, dim3(T / 128, B * Hq),
+                       dim3(256), 0, cur_stream(), qp, kp, vp, op, lse_ptr,
+                       B, Hq, Hkv, T, Tk, c, qo, scale);
   if (want_lse) return {o, lse};
   return {o};
 }
@@ -625,7 +627,8 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
   int Hkv = (int)k.size(1);
   TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   TORCH_CHECK(!bthd || T % 256 == 0,
-              "BTHD layout needs the v4 kernels (T % 256 == 0)");
+              "BTHD-view layout needs T % 256 == 0: only the 256-row "
+              "kernels read it");
   int D = (int)q.size(3);
   auto mk_like = [&](const at::Tensor& t, int H) {
     return bthd ? at::empty({B, T, H, D}, t.options()).permute({0, 2, 1, 3})
@@ -637,150 +640,44 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
   auto dsum = at::empty({B, Hq, T}, q.options().dtype(at::kFloat));
   float scale = 1.0f / sqrtf((float)q.size(3));
   long long rows = (long long)B * Hq * T;
+  const short* qp = (const short*)q.data_ptr();
+  const short* kp = (const short*)k.data_ptr();
+  const short* vp = (const short*)v.data_ptr();
+  const short* dop = (const short*)d_o.data_ptr();
+  const float* lsep = lse.data_ptr<float>();
+  float* dsp = dsum.data_ptr<float>();
+  short* dqp = (short*)dq.data_ptr();
+  short* dkp = (short*)dk.data_ptr();
+  short* dvp = (short*)dv.data_ptr();
+  const int c = causal ? 1 : 0;
+  hipStream_t st = cur_stream();
   hipLaunchKernelGGL(fa_bwd_prep_bf16, dim3((rows + 3) / 4), dim3(256), 0,
-                     cur_stream(), (const short*)d_o.data_ptr(),
-                     (const short*)o.data_ptr(), dsum.data_ptr<float>(),
-                     rows, Hq, T, bthd);
-  static const bool split = getenv("RAY_AMD_FA_BWD_FUSED") == nullptr;
-  static const bool v3 = getenv("RAY_AMD_FA_BWD_V2") == nullptr;
-  TORCH_CHECK(!bthd || (split && v3),
-              "BTHD layout requires the v3/v4 backward path");
-  // dq v4 (8-wave + tr16 K-gathers) measured 12.68 vs v3 13.15 ms
-  // whole-bwd; the pre-tr16 v4 had regressed — tr16 flipped it
-  // dq v5: 64-row K/V tiles, split (issue-early / write-late) staging.
-  // RAY_AMD_FA_NO_DQ_V5 selects v4.
-  if (v3 && T % 256 == 0 && getenv("RAY_AMD_FA_NO_DQ_V4") == nullptr &&
-      getenv("RAY_AMD_FA_NO_DQ_V5") == nullptr) {
-    hipLaunchKernelGGL(fa_bwd_dq_v5_bf16, dim3(T / 256, B * Hq),
-                       dim3(512), 0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dq.data_ptr(), B, Hq,
-                       Hkv, T, causal ? 1 : 0, scale, bthd);
-  } else if (v3 && T % 256 == 0 && getenv("RAY_AMD_FA_NO_DQ_V4") == nullptr)
-    hipLaunchKernelGGL(fa_bwd_dq_v4_bf16, dim3(T / 256, B * Hq), dim3(512),
-                       0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dq.data_ptr(), B, Hq,
-                       Hkv, T, causal ? 1 : 0, scale, bthd);
-  else if (v3)
-    hipLaunchKernelGGL(fa_bwd_dq_v3_bf16, dim3(T / 128, B * Hq), dim3(256),
-                       0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dq.data_ptr(), B, Hq,
-                       Hkv, T, causal ? 1 : 0, scale, bthd);
-  else
-    hipLaunchKernelGGL(fa_bwd_dq_bf16, dim3(T / 128, B * Hq), dim3(256), 0,
-                       cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dq.data_ptr(), B, Hq,
-                       Hkv, T, causal ? 1 : 0, scale);
-  if (split && v3) {
-    // v3/v4: K/V register-resident, 64-row dbuf staged q/dO tiles,
-    // swizzled LDS reads, one barrier per tile; v4 = 8-wave blocks
-    // (256 kv rows) when the shape allows
-    bool v4 = (T % 256 == 0) &&
-              (bthd || getenv("RAY_AMD_FA_BWD_V3ONLY") == nullptr);
-    if (v4 && getenv("RAY_AMD_FA_NO_DKV5") == nullptr &&
-        getenv("RAY_AMD_FA_NO_DKV6") == nullptr) {
-      // v6: key on the MFMA lane, so P and dS feed the dV^T / dK^T
-      // products from registers; split staging; whole-row epilogue.
-      // Key block is the slow grid dimension (heaviest causal block
-      // first) unless RAY_AMD_FA_DKV6_KB_FAST asks for v5's order.
-      const int kb_slow = getenv("RAY_AMD_FA_DKV6_KB_FAST") == nullptr;
-      hipLaunchKernelGGL(fa_bwd_dkv_v6_bf16,
-                         kb_slow ? dim3(B * Hkv, T / 256)
-                                 : dim3(T / 256, B * Hkv),
-                         dim3(512), 0, cur_stream(),
-                         (const short*)q.data_ptr(),
-                         (const short*)k.data_ptr(),
-                         (const short*)v.data_ptr(),
-                         (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                         dsum.data_ptr<float>(), (short*)dk.data_ptr(),
-                         (short*)dv.data_ptr(), B, Hq, Hkv, T,
-                         causal ? 1 : 0, scale, bthd, kb_slow);
-      return {dq, dk, dv};
-    }
-    if (v4 && getenv("RAY_AMD_FA_NO_DKV5") == nullptr) {
-      // v5: fused dK+dV — S and dP computed once per tile, half the
-      // Q/dO staging; V comes from LDS to stay at 2 waves/SIMD
-      hipLaunchKernelGGL(fa_bwd_dkv_v5_bf16, dim3(T / 256, B * Hkv),
-                         dim3(512), 0, cur_stream(),
-                         (const short*)q.data_ptr(),
-                         (const short*)k.data_ptr(),
-                         (const short*)v.data_ptr(),
-                         (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                         dsum.data_ptr<float>(), (short*)dk.data_ptr(),
-                         (short*)dv.data_ptr(), B, Hq, Hkv, T,
-                         causal ? 1 : 0, scale, bthd);
-      return {dq, dk, dv};
-    }
-    if (v4) {
-      hipLaunchKernelGGL(fa_bwd_dv_v4_bf16, dim3(T / 256, B * Hkv),
-                         dim3(512), 0, cur_stream(),
-                         (const short*)q.data_ptr(),
-                         (const short*)k.data_ptr(),
-                         (const short*)v.data_ptr(),
-                         (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                         (short*)dv.data_ptr(), B, Hq, Hkv, T,
-                         causal ? 1 : 0, scale, bthd);
-      hipLaunchKernelGGL(fa_bwd_dk_v4_bf16, dim3(T / 256, B * Hkv),
-                         dim3(512), 0, cur_stream(),
-                         (const short*)q.data_ptr(),
-                         (const short*)k.data_ptr(),
-                         (const short*)v.data_ptr(),
-                         (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                         dsum.data_ptr<float>(), (short*)dk.data_ptr(), B,
-                         Hq, Hkv, T, causal ? 1 : 0, scale, bthd);
-      return {dq, dk, dv};
-    }
-    hipLaunchKernelGGL(fa_bwd_dv_v3_bf16, dim3(T / 128, B * Hkv),
-                       dim3(256), 0, cur_stream(),
-                       (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       (short*)dv.data_ptr(), B, Hq, Hkv, T,
-                       causal ? 1 : 0, scale);
-    hipLaunchKernelGGL(fa_bwd_dk_v3_bf16, dim3(T / 128, B * Hkv),
-                       dim3(256), 0, cur_stream(),
-                       (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dk.data_ptr(), B,
-                       Hq, Hkv, T, causal ? 1 : 0, scale);
-    return {dq, dk, dv};
-  }
-  if (split) {
-    // dk/dv split: each kernel fits 2 waves/SIMD (the fused one is
-    // register-bound to 1) at +25% mfma work — measured faster
-    hipLaunchKernelGGL(fa_bwd_dv_bf16, dim3(T / 128, B * Hkv), dim3(256),
-                       0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       (short*)dv.data_ptr(), B, Hq, Hkv, T,
-                       causal ? 1 : 0, scale);
-    hipLaunchKernelGGL(fa_bwd_dk_bf16, dim3(T / 128, B * Hkv), dim3(256),
-                       0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dk.data_ptr(), B,
-                       Hq, Hkv, T, causal ? 1 : 0, scale);
+                     st, dop, (const short*)o.data_ptr(), dsp, rows, Hq, T,
+                     bthd);
+  if (T % 256 == 0) {
+    // 256-row blocks, either layout. dq: 64-row K/V tiles, split (issue
+    // early / write late) staging. dkv: key on the MFMA lane, so P and dS
+    // feed the dV^T / dK^T products from registers; its grid has the key
+    // block as the slow dimension (heaviest causal block first).
+    hipLaunchKernelGGL(fa_bwd_dq_v5_bf16, dim3(T / 256, B * Hq), dim3(512),
+                       0, st, qp, kp, vp, dop, lsep, dsp, dqp, B, Hq, Hkv, T,
+                       c, scale, bthd);
+    hipLaunchKernelGGL(fa_bwd_dkv_v6_bf16, dim3(B * Hkv, T / 256), dim3(512),
+                       0, st, qp, kp, vp, dop, lsep, dsp, dkp, dvp, B, Hq,
+                       Hkv, T, c, scale, bthd);
   } else {
-    hipLaunchKernelGGL(fa_bwd_dkv_bf16, dim3(T / 128, B * Hkv), dim3(256),
-                       0, cur_stream(), (const short*)q.data_ptr(),
-                       (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(),
-                       (const short*)d_o.data_ptr(), lse.data_ptr<float>(),
-                       dsum.data_ptr<float>(), (short*)dk.data_ptr(),
-                       (short*)dv.data_ptr(), B, Hq, Hkv, T,
-                       causal ? 1 : 0, scale);
+    // 128-row blocks, contiguous BHTD only (checked above): K/V
+    // register-resident, 64-row double-buffered q/dO tiles; dV and dK are
+    // separate kernels so that each fits 2 waves/SIMD.
+    const dim3 blk(256);
+    hipLaunchKernelGGL(fa_bwd_dq_v3_bf16, dim3(T / 128, B * Hq), blk, 0, st,
+                       qp, kp, vp, dop, lsep, dsp, dqp, B, Hq, Hkv, T, c,
+                       scale, /*bthd=*/0);
+    hipLaunchKernelGGL(fa_bwd_dv_v3_bf16, dim3(T / 128, B * Hkv), blk, 0, st,
+                       qp, kp, vp, dop, lsep, dvp, B, Hq, Hkv, T, c, scale);
+    hipLaunchKernelGGL(fa_bwd_dk_v3_bf16, dim3(T / 128, B * Hkv), blk, 0, st,
+                       qp, kp, vp, dop, lsep, dsp, dkp, B, Hq, Hkv, T, c,
+                       scale);
   }
   return {dq, dk, dv};
 }

@@ -618,7 +618,7 @@ def img_normalize(x_u8: torch.Tensor, mean: torch.Tensor, std: torch.Tensor):
 
 
 # --------------------------------------------------------------------------
-# Flash attention (forward; fused CDNA4 kernel with LSE output)
+# Flash attention (fused CDNA4 forward with LSE output, and backward)
 # --------------------------------------------------------------------------
 
 
@@ -653,20 +653,25 @@ def _is_bthd_view(t):
             and st[0] == H * T * D)
 
 
+def _attn_operands(q, k, v):
+    """q, k, v in a layout the kernels read, and whether that is the BTHD
+    view: the tensors as they are if T % 256 == 0 and all three are BTHD
+    views (only the 256-row kernels read those), else contiguous copies."""
+    if q.shape[2] % 256 == 0 and _is_bthd_view(q) and _is_bthd_view(k) \
+            and _is_bthd_view(v):
+        return q, k, v, True
+    return q.contiguous(), k.contiguous(), v.contiguous(), False
+
+
 class _FlashAttnFn(torch.autograd.Function):
-    """Training flash attention: v5 forward + FA2-style two-kernel
-    backward (csrc/hip/fa_bwd.hip). Requires T == Tk, T % 128 == 0,
-    D == 128 (the Llama training shape)."""
+    """Training flash attention: HIP forward with LSE, then the prep, dQ
+    and dK/dV backward kernels (csrc/ops.hip picks the 256-row or the
+    128-row set from T). Requires T == Tk, T % 128 == 0, D == 128 (the
+    Llama training shape)."""
 
     @staticmethod
     def forward(ctx, q, k, v, causal):
-        T = q.shape[2]
-        bthd = (T % 256 == 0 and _is_bthd_view(q) and _is_bthd_view(k)
-                and _is_bthd_view(v))
-        if bthd:
-            qc, kc, vc = q, k, v
-        else:
-            qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+        qc, kc, vc, bthd = _attn_operands(q, k, v)
         out, lse = _K.flash_attn_fwd(qc, kc, vc, causal, 0, True)
         ctx.save_for_backward(qc, kc, vc, out, lse)
         ctx.causal = causal
@@ -706,7 +711,8 @@ def flash_attention(q, k, v, causal: bool = True, q_offset: int = 0,
         if return_lse or q_offset:
             raise NotImplementedError(
                 "flash_attention backward does not support return_lse/"
-                "q_offset (ring-attention bwd lands next round)"
+                "q_offset (ring attention calls the backward kernels "
+                "itself, see ray_amd/parallel/sequence.py)"
             )
         if T % 128 != 0 or T != k.shape[2]:
             raise NotImplementedError(
@@ -717,12 +723,9 @@ def flash_attention(q, k, v, causal: bool = True, q_offset: int = 0,
     pad = (-T) % 128
     if pad:
         q = torch.nn.functional.pad(q, (0, 0, 0, pad))
-    if not pad and T % 256 == 0 and _is_bthd_view(q) and _is_bthd_view(k) \
-            and _is_bthd_view(v):
-        r = _K.flash_attn_fwd(q, k, v, causal, q_offset, return_lse)
-    else:
-        r = _K.flash_attn_fwd(q.contiguous(), k.contiguous(),
-                              v.contiguous(), causal, q_offset, return_lse)
+    # a padded q is a contiguous copy, never a BTHD view
+    qc, kc, vc, _ = _attn_operands(q, k, v)
+    r = _K.flash_attn_fwd(qc, kc, vc, causal, q_offset, return_lse)
     out = r[0][:, :, :T] if pad else r[0]
     if return_lse:
         lse = r[1][:, :, :T] if pad else r[1]

@@ -29,8 +29,6 @@ def run(tag):
     print(f"{tag}: err={err:.3f} lse_err={lse_err:.4f}  {dt*1000:.2f} ms  {flops/dt/1e12:.0f} TF")
 
 run("fa-default")
-os.environ["RAY_AMD_FA_V2"]="1"
-# env is read once (static); need subprocess for A/B — done by caller
 # sdpa reference
 B,Hq,Hkv,T,D = 8,32,8,4096,128
 q = torch.randn(B,Hq,T,D, device="cuda", dtype=torch.bfloat16)

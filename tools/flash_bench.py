@@ -1,7 +1,8 @@
-"""Flash-attention forward throughput on MI355X (evidence for profiles/).
+"""Flash-attention throughput on MI355X (evidence for profiles/).
 
-Measures ray_amd.ops.flash_attention (HIP v5 kernel) vs torch SDPA on
-the Llama-3-8B prefill shape, plus max error vs an fp32 reference.
+Measures ray_amd.ops.flash_attention vs torch SDPA on the Llama-3-8B
+prefill shape (T % 256 == 0, so the 256-row HIP kernels): forward, plus
+max error vs an fp32 reference, then the fwd+bwd round trip.
 """
 import os
 import sys
