@@ -10,6 +10,8 @@ from ray_amd import serve
 from ray_amd.llm import build_llm_deployment
 
 ray.init()
+# Shared system prompts: add "batching": "continuous", "kv_cache": "paged",
+# "enable_prefix_caching": True (and "prefill_chunk_tokens": 512 for long ones).
 app = build_llm_deployment(
     {"model_id": "llama-tiny", "max_seq_len": 128, "use_hip_graph": False}
 )

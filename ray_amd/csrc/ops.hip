@@ -21,6 +21,7 @@
 #include "hip/fa_bwd_dkv_v6.hip"
 #include "hip/gemv.hip"
 #include "hip/paged_attn.hip"
+#include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
 
 #define CHECK_IN(x)                                                     \
@@ -287,6 +288,70 @@ at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
 #undef PA_REP
 #undef PA_LAUNCH
   if (S > 1) launch_paged_reduce(ws, out, B, Hq, D, S);
+  return out;
+}
+
+// Chunk prefill over the paged cache: q [B, Tq, Hq, D] at positions
+// ctx_lens[b] .. ctx_lens[b]+Tq-1, whose own K/V are already appended.
+at::Tensor paged_attn_prefill(at::Tensor q, at::Tensor k_cache,
+                              at::Tensor v_cache, at::Tensor block_table,
+                              at::Tensor ctx_lens, at::Tensor q_lens) {
+  CHECK_IN(q);
+  CHECK_I32(block_table);
+  CHECK_I32(ctx_lens);
+  CHECK_I32(q_lens);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
+  TORCH_CHECK(q.dim() == 4, "q must be [B, Tq, Hq, D]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "paged_attn_prefill: q must be 16-byte aligned");
+  int B = (int)q.size(0), Hq = (int)q.size(2), D = (int)q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
+  int Hkv = (int)k_cache.size(1);
+  check_paged_cache(k_cache, v_cache, Hkv, D);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
+              "paged_attn_prefill: caches must be 16-byte aligned");
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  int rep = Hq / Hkv;
+  TORCH_CHECK(rep == 1 || rep == 2 || rep == 4 || rep == 8,
+              "paged_attn: Hq/Hkv must be 1, 2, 4 or 8");
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+              block_table.size(1) >= 1,
+              "block_table must be [B, max_pages]");
+  TORCH_CHECK(block_table.size(1) <= (1 << 26),
+              "paged_attn_prefill: block table too wide");
+  TORCH_CHECK(ctx_lens.dim() == 1 && ctx_lens.size(0) == B &&
+              q_lens.dim() == 1 && q_lens.size(0) == B,
+              "ctx_lens and q_lens must be [B]");
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) <= (1 << 26),
+              "paged_attn_prefill: Tq must be 1..2^26");
+  int Tq = (int)q.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && Hq <= 65535,
+              "paged_attn_prefill: B and Hq must fit a grid dimension");
+  auto out = at::empty_like(q);
+  // 128-row query tiles (4 waves) while they are what fills the GPU;
+  // once there are two such blocks for each of the 256 CUs, 256-row
+  // tiles (8 waves) stage every K/V tile half as often per query row
+  const long long blocks128 = (long long)((Tq + 127) / 128) * Hq * B;
+  const int waves = blocks128 >= PP_WIDE_TILE_BLOCKS ? 8 : 4;
+  dim3 grid((Tq + 32 * waves - 1) / (32 * waves), Hq, B);
+#define PP_LAUNCH(DD, WW)                                                   \
+  hipLaunchKernelGGL((paged_attn_prefill_bf16<DD, WW>), grid,               \
+                     dim3(64 * WW), 0, cur_stream(),                        \
+                     (const short*)q.data_ptr(),                            \
+                     (const short*)k_cache.data_ptr(),                      \
+                     (const short*)v_cache.data_ptr(),                      \
+                     block_table.data_ptr<int>(), ctx_lens.data_ptr<int>(), \
+                     q_lens.data_ptr<int>(), (short*)out.data_ptr(), Tq,    \
+                     Hq, Hkv, (int)k_cache.size(0),                         \
+                     (int)block_table.size(1), 1.0f / sqrtf((float)D))
+  if (D == 64) {
+    if (waves == 4) { PP_LAUNCH(64, 4); } else { PP_LAUNCH(64, 8); }
+  } else {
+    if (waves == 4) { PP_LAUNCH(128, 4); } else { PP_LAUNCH(128, 8); }
+  }
+#undef PP_LAUNCH
   return out;
 }
 
@@ -696,6 +761,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("workspace") = py::none());
   m.def("paged_attn_reduce", &paged_attn_reduce);
   m.def("rope_append_paged", &rope_append_paged);
+  m.def("paged_attn_prefill", &paged_attn_prefill);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

@@ -35,6 +35,12 @@ class LLMConfig:
     # reserved null page; default fits max_batch_size x max_seq_len.
     kv_cache: str = "contiguous"
     kv_num_pages: Optional[int] = None
+    # Paged cache only. enable_prefix_caching: prompts that start with
+    # the same full 16-token pages share those pages and skip their
+    # prefill. prefill_chunk_tokens: run a prompt through the model at
+    # most that many tokens at a time.
+    enable_prefix_caching: bool = False
+    prefill_chunk_tokens: Optional[int] = None
 
 
 class LLMEngine:
@@ -171,12 +177,21 @@ class ContinuousBatchingEngine:
                 f"kv_cache must be 'contiguous' or 'paged', got "
                 f"{config.kv_cache!r}")
         self._paged = config.kv_cache == "paged"
+        if not self._paged and (config.enable_prefix_caching
+                                or config.prefill_chunk_tokens is not None):
+            raise ValueError(
+                "enable_prefix_caching and prefill_chunk_tokens need "
+                "kv_cache='paged'")
         if self._paged:
             from ray_amd.llm.paged import PagedDecoder
 
             self.decoder = PagedDecoder(self.model, self.B, self.max_T,
                                         self.device,
-                                        num_pages=config.kv_num_pages)
+                                        num_pages=config.kv_num_pages,
+                                        prefix_caching=(
+                                            config.enable_prefix_caching),
+                                        prefill_chunk=(
+                                            config.prefill_chunk_tokens))
             if config.use_hip_graph and self.device.type == "cuda":
                 self.decoder.capture()
         else:
@@ -199,6 +214,10 @@ class ContinuousBatchingEngine:
             pool = self.decoder.pool
             self.stats["kv_pages_total"] = pool.num_usable
             self.stats["kv_pages_free"] = pool.num_free
+            self.stats["kv_pages_cached"] = pool.num_cached
+            self.stats["prefix_hit_tokens"] = self.decoder.prefix_hit_tokens
+            self.stats["prefill_tokens_computed"] = (
+                self.decoder.prefill_tokens_computed)
 
     def _reserve_tokens(self, prompt_len: int, max_new_tokens: int) -> int:
         """KV rows a request can ever occupy (prompt + decode budget)."""

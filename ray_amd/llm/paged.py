@@ -9,7 +9,8 @@ length.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from collections import OrderedDict
+from typing import Dict, List, Optional
 
 import torch
 
@@ -23,10 +24,20 @@ def pages_for(tokens: int, page_size: int = PAGE_SIZE) -> int:
 
 
 class PagedKVPool:
-    """Per-layer K/V page tensors [num_pages, Hkv, page_size, D] and a
-    host free list. Page 0 is the reserved null page: block tables are
-    zero-filled, so an unused entry points at memory that is inside the
-    allocation and never part of any sequence. It is never handed out."""
+    """Per-layer K/V page tensors [num_pages, Hkv, page_size, D], a host
+    free list with reference counts, and a prefix index. Page 0 is the
+    reserved null page: block tables are zero-filled, so an unused entry
+    points at memory that is inside the allocation and never part of any
+    sequence. It is never handed out.
+
+    Prefix index: a full prompt page is keyed by (parent, its page_size
+    token ids), where parent is the node id of the page before it (0 at
+    the root). Node ids are never reused, so an entry whose ancestor was
+    evicted can no longer be reached. One page id addresses every
+    layer's tensors, so the index is per pool. An indexed page whose
+    count drops to 0 keeps its contents and waits in an LRU; alloc takes
+    from the free list first and evicts from the LRU only when that is
+    empty. While nothing is registered the pool is a plain free list."""
 
     def __init__(self, num_layers: int, num_pages: int, Hkv: int, D: int,
                  device, dtype=torch.bfloat16, page_size: int = PAGE_SIZE):
@@ -43,36 +54,124 @@ class PagedKVPool:
         self.v = [torch.empty_like(k) for k in self.k]
         # pop() hands out low page numbers first
         self._free: List[int] = list(range(num_pages - 1, 0, -1))
-        self._used = set()
+        self._ref: Dict[int, int] = {}       # allocated page -> count >= 1
+        self._index: Dict[tuple, int] = {}   # (parent node, tokens) -> page
+        self._page_key: Dict[int, tuple] = {}  # indexed page -> its key
+        self._node: Dict[int, int] = {}      # indexed page -> its node id
+        self._next_node = 1
+        # indexed pages with count 0, oldest (first to be evicted) first
+        self._lru: "OrderedDict[int, None]" = OrderedDict()
 
     @property
     def num_free(self) -> int:
-        return len(self._free)
+        """Pages alloc can hand out: free ones plus evictable cached
+        ones."""
+        return len(self._free) + len(self._lru)
+
+    @property
+    def num_cached(self) -> int:
+        """Pages held in the prefix index, in use or evictable."""
+        return len(self._page_key)
 
     @property
     def num_usable(self) -> int:
         return self.num_pages - 1
 
+    def _drop_index(self, p: int):
+        del self._index[self._page_key.pop(p)]
+        del self._node[p]
+
     def alloc(self, n: int) -> Optional[List[int]]:
-        """n pages, or None (and nothing taken) when the pool is short."""
+        """n pages with count 1, or None (and nothing taken) when the
+        pool is short."""
         if n < 0:
             raise ValueError("alloc of a negative page count")
-        if n > len(self._free):
+        if n > self.num_free:
             return None
-        pages = [self._free.pop() for _ in range(n)]
-        self._used.update(pages)
+        pages = []
+        for _ in range(n):
+            if self._free:
+                p = self._free.pop()
+            else:
+                p, _ = self._lru.popitem(last=False)
+                self._drop_index(p)
+            self._ref[p] = 1
+            pages.append(p)
         return pages
 
+    def share(self, pages: List[int]):
+        """Take one more reference on each allocated page."""
+        pages = list(pages)
+        for p in pages:
+            if p not in self._ref:
+                raise ValueError(f"share: page {p} is not allocated")
+        for p in pages:
+            self._ref[p] += 1
+
     def free(self, pages: List[int]):
+        """Drop one reference per page. A page at count 0 returns to the
+        free list, or, if it is indexed, to the back of the LRU: pass a
+        sequence's pages deepest-first so chains are evicted from the
+        tail."""
         pages = list(pages)
         if len(set(pages)) != len(pages):
             raise ValueError(f"free: page listed twice in {pages}")
         for p in pages:
-            if p not in self._used:
+            if p not in self._ref:
                 raise ValueError(f"free: page {p} is not allocated")
         for p in pages:
-            self._used.remove(p)
-            self._free.append(p)
+            self._ref[p] -= 1
+            if self._ref[p] == 0:
+                del self._ref[p]
+                if p in self._page_key:
+                    self._lru[p] = None
+                else:
+                    self._free.append(p)
+
+    def _page_tokens(self, tokens, i: int) -> tuple:
+        ps = self.page_size
+        return tuple(int(t) for t in tokens[i * ps:(i + 1) * ps])
+
+    def match_prefix(self, tokens, max_pages: int) -> List[int]:
+        """Longest run of indexed full pages that spell the start of
+        `tokens`, at most max_pages long, with a reference taken on
+        each."""
+        pages: List[int] = []
+        parent = 0
+        for i in range(min(max_pages, len(tokens) // self.page_size)):
+            p = self._index.get((parent, self._page_tokens(tokens, i)))
+            if p is None:
+                break
+            if p in self._ref:
+                self._ref[p] += 1
+            else:
+                del self._lru[p]
+                self._ref[p] = 1
+            pages.append(p)
+            parent = self._node[p]
+        return pages
+
+    def register_prefix(self, tokens, pages: List[int]):
+        """Index every full page of the prompt `tokens`, held in
+        `pages` (allocated, in order), that is not indexed yet. A key
+        that is already present keeps its first page."""
+        parent = 0
+        for i in range(min(len(pages), len(tokens) // self.page_size)):
+            key = (parent, self._page_tokens(tokens, i))
+            p = self._index.get(key)
+            if p is None:
+                p = pages[i]
+                if p not in self._ref:
+                    raise ValueError(
+                        f"register_prefix: page {p} is not allocated")
+                if p in self._page_key:
+                    # already spells another chain: leave it there
+                    return
+                self._index[key] = p
+                self._page_key[p] = key
+                self._node[p] = self._next_node
+                self._next_node += 1
+            parent = self._node[p]
 
 
 class _PagedSlotCache:
@@ -110,7 +209,15 @@ class PagedDecoder:
     sequence lengths."""
 
     def __init__(self, model, batch_size: int, max_T: int, device,
-                 num_pages: Optional[int] = None):
+                 num_pages: Optional[int] = None,
+                 prefix_caching: bool = False,
+                 prefill_chunk: Optional[int] = None):
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError("prefill_chunk must be at least 1")
+        self.prefix_caching = prefix_caching
+        self.prefill_chunk = prefill_chunk
+        self.prefix_hit_tokens = 0        # prompt tokens served from pages
+        self.prefill_tokens_computed = 0  # prompt tokens run through the model
         self.m = model
         cfg = model.cfg
         self.B = batch_size
@@ -150,7 +257,11 @@ class PagedDecoder:
     def release_slot(self, slot: int):
         """Return the slot's pages to the pool; the slot goes inactive."""
         if self._slot_pages[slot]:
-            self.pool.free(self._slot_pages[slot])
+            # a decrement: shared pages live on under their other
+            # owners. With prefix caching the deepest page goes first,
+            # so that cached chains are evicted from their tail.
+            pages = self._slot_pages[slot]
+            self.pool.free(pages[::-1] if self.prefix_caching else pages)
             self._slot_pages[slot] = []
         self.block_table[slot].zero_()
         self.seq_lens[slot] = 0
@@ -188,6 +299,10 @@ class PagedDecoder:
         if n > self.max_T:
             raise ValueError(f"prompt of {n} tokens exceeds max_T "
                              f"{self.max_T}")
+        if self.prefix_caching or self.prefill_chunk is not None:
+            return self._prefill_slot_paged(slot, toks,
+                                            max(reserve_tokens, n))
+        self.prefill_tokens_computed += n
         pages = self.reserve_slot(slot, max(reserve_tokens, n))
         page_ids = torch.tensor(pages, dtype=torch.long, device=self.device)
         caches = [
@@ -198,6 +313,89 @@ class PagedDecoder:
         logits = self.m(toks.view(1, -1), kv_caches=caches, pos0=0)[0, -1]
         self.set_slot_len(slot, n)
         return logits
+
+    @torch.no_grad()
+    def _prefill_slot_paged(self, slot: int, toks: torch.Tensor,
+                            reserve_tokens: int):
+        """Prefill through the paged prefill kernel: reuse the cached
+        pages that spell the start of the prompt, then run the rest in
+        chunks that attend to the pages directly.
+
+        Invariant: shared pages are read-only. Only full prompt pages
+        are ever shared; chunk writes start at row 16 * (shared pages)
+        and decode appends at rows >= n, both past every shared page."""
+        n = toks.numel()
+        if n < 1:
+            raise ValueError("prefill of an empty prompt")
+        ps = self.pool.page_size
+        self.release_slot(slot)
+        need = pages_for(min(reserve_tokens, self.max_T))
+        tok_list = toks.tolist()
+        shared: List[int] = []
+        if self.prefix_caching:
+            # at most (n-1)//ps pages: at least one token is computed,
+            # so there are last-position logits
+            shared = self.pool.match_prefix(tok_list, (n - 1) // ps)
+        fresh = self.pool.alloc(need - len(shared))
+        if fresh is None:
+            self.pool.free(shared[::-1])
+            raise RuntimeError(
+                f"paged KV pool exhausted: need {need - len(shared)} pages, "
+                f"{self.pool.num_free} free")
+        pages = shared + fresh
+        self._slot_pages[slot] = pages
+        row = torch.zeros(self.max_pages, dtype=torch.int32)
+        row[: len(pages)] = torch.tensor(pages, dtype=torch.int32)
+        self.block_table[slot].copy_(row)
+
+        ctx = len(shared) * ps
+        chunk = self.prefill_chunk or (n - ctx)
+        logits = None
+        for pos0 in range(ctx, n, chunk):
+            end = min(pos0 + chunk, n)
+            logits = self._prefill_chunk(slot, toks[pos0:end], pos0,
+                                         last=end == n)
+        self.prefix_hit_tokens += ctx
+        self.prefill_tokens_computed += n - ctx
+        if self.prefix_caching:
+            self.pool.register_prefix(tok_list, pages[: n // ps])
+        self.set_slot_len(slot, n)
+        return logits
+
+    def _prefill_chunk(self, slot: int, toks: torch.Tensor, pos0: int,
+                       last: bool = True):
+        """Run prompt tokens pos0 .. pos0+T-1 of one slot: per layer,
+        append their rotated K and raw V to the slot's pages, then
+        attend to the pages (append-then-attend, as the decode step).
+        Returns last-position logits [V] when `last`, else None."""
+        m = self.m
+        T = toks.numel()
+        ps = self.pool.page_size
+        dev = self.device
+        x = m.embed(toks.view(1, T))
+        cos, sin = m.cosT[pos0 : pos0 + T], m.sinT[pos0 : pos0 + T]
+        t = torch.arange(pos0, pos0 + T, device=dev)
+        pg = self.block_table[slot, t // ps].long()
+        sl = t % ps
+        bt = self.block_table[slot : slot + 1]
+        ctx_lens = torch.tensor([pos0], dtype=torch.int32, device=dev)
+        q_lens = torch.tensor([T], dtype=torch.int32, device=dev)
+        for li, layer in enumerate(m.layers):
+            at = layer.attn
+            q, k, v = at.qkv(layer.attn_norm(x))
+            q = ops.rope(q, cos, sin)
+            k = ops.rope(k, cos, sin)
+            kp, vp = self.pool.k[li], self.pool.v[li]
+            # [1,T,Hkv,D] -> rows pos0.. of the slot's pages
+            kp[pg, :, sl] = k[0].to(kp.dtype)
+            vp[pg, :, sl] = v[0].to(vp.dtype)
+            attn = ops.paged_attention_prefill(q.contiguous(), kp, vp, bt,
+                                               ctx_lens, q_lens)
+            x = x + at.o_proj(attn.reshape(1, T, -1))
+            x = x + layer.mlp(layer.mlp_norm(x))
+        if not last:
+            return None
+        return m.lm_head(m.final_norm(x[:, -1:]))[0, -1]
 
     # ---- decode -----------------------------------------------------
 

@@ -833,3 +833,55 @@ def rope_append_paged(q, k, v, cosT, sinT, pos, block_table, k_cache,
     _require_ext("rope_append_paged")
     return _K.rope_append_paged(q, k, v, cosT, sinT, pos, block_table,
                                 k_cache, v_cache)
+
+
+# --------------------------------------------------------------------------
+# Paged-KV prefill attention (serving; csrc/hip/paged_attn_prefill.hip)
+# --------------------------------------------------------------------------
+
+
+def paged_attention_prefill_ref(q, k_cache, v_cache, block_table, ctx_lens,
+                                q_lens):
+    """fp32 reference. q [B,Tq,Hq,D] is a chunk of queries at positions
+    ctx_lens[b] .. ctx_lens[b]+Tq-1 whose own K/V are already in the
+    pages. Gathers each row's pages as paged_attention_ref does, then
+    masks causally with the ctx offset: query row i sees cache rows
+    j <= ctx_lens[b] + i. Rows i >= q_lens[b] are zeros."""
+    import math
+
+    B, Tq, Hq, D = q.shape
+    _, Hkv, page, _ = k_cache.shape
+    rep = Hq // Hkv
+    out = torch.zeros(B, Tq, Hq, D, dtype=torch.float32, device=q.device)
+    ctxs, qls = ctx_lens.tolist(), q_lens.tolist()
+    for b in range(B):
+        ctx, n = int(ctxs[b]), min(int(qls[b]), Tq)
+        if n <= 0:
+            continue
+        L = ctx + n
+        pages = block_table[b, : (L + page - 1) // page].long()
+        # [P,Hkv,page,D] -> [Hkv, P*page, D]
+        k = k_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :L]
+        v = v_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :L]
+        kf = k.float().repeat_interleave(rep, dim=0)
+        vf = v.float().repeat_interleave(rep, dim=0)
+        s = torch.einsum("thd,hjd->htj", q[b, :n].float(), kf) / math.sqrt(D)
+        i = torch.arange(n, device=q.device).view(n, 1)
+        j = torch.arange(L, device=q.device).view(1, L)
+        s = s.masked_fill(j > ctx + i, float("-inf"))
+        out[b, :n] = torch.einsum("htj,hjd->thd", torch.softmax(s, -1), vf)
+    return out.to(q.dtype)
+
+
+def paged_attention_prefill(q, k_cache, v_cache, block_table, ctx_lens,
+                            q_lens):
+    """Causal attention from a chunk of query tokens to a paged KV
+    cache. q [B,Tq,Hq,D] bf16 contiguous -> [B,Tq,Hq,D]; ctx_lens [B]
+    int32 rows cached before the chunk, q_lens [B] int32 valid query
+    rows. The chunk's K/V must already be appended to the pages."""
+    if not q.is_cuda:
+        return paged_attention_prefill_ref(q, k_cache, v_cache, block_table,
+                                           ctx_lens, q_lens)
+    _require_ext("paged_attention_prefill")
+    return _K.paged_attn_prefill(q, k_cache, v_cache, block_table, ctx_lens,
+                                 q_lens)
