@@ -7,7 +7,7 @@
 // sequence b sits at position ctx_lens[b] + i and sees cache rows
 // j <= ctx_lens[b] + i. Rows i >= q_lens[b] are written as zeros.
 //
-// paged_attn_prefill_bf16<D, WAVES>: grid (ceil(Tq/(32*WAVES)), Hq, B),
+// paged_attn_prefill_kernel<D, WAVES, FP8>: grid (ceil(Tq/(32*WAVES)), Hq, B),
 // WAVES x 32 query rows per block. The binding launches 4 waves
 // (128-row tiles) until those make PP_WIDE_TILE_BLOCKS blocks, then 8
 // (256-row tiles, which stage each K/V tile half as often per query
@@ -18,8 +18,8 @@
 // with the same fragment layouts and K XOR-swizzle. What differs is the
 // staging: a KV tile is 64 tokens = 4 pages; each 16-row slab of a tile
 // is the contiguous PAGE*D block of one (page, kv head), found through
-// the block table, clamped into the pool, and copied with 16-byte
-// loads into double-buffered LDS while the previous tile computes.
+// the block table, clamped into the pool, and copied in 8-element
+// chunks into double-buffered LDS while the previous tile computes.
 //
 // Cache rows at or beyond ctx + q_len (tail slots of the last page,
 // unused table entries, the null page) are never loaded: they are
@@ -29,6 +29,15 @@
 // split over KV: the query-tile grid is the parallelism at prefill
 // sizes. Query tiles are issued last-first so the longest ones start
 // first.
+//
+// FP8 caches (FP8 = true) hold OCP e4m3fn bytes, value = byte * scale.
+// Only the staging differs: a chunk is 8 bytes instead of 16, and the
+// LDS write converts fp8 -> f32 -> bf16 in registers (exact: e4m3 has 3
+// mantissa bits), so LDS holds the same bf16 image, swizzle included,
+// and everything after it is the bf16 code. k_scale is folded into
+// `scale` by the binding, v_scale (oscale) into the final 1/l.
+#include <type_traits>
+
 #include "common.h"
 
 #define PP_PAGE 16
@@ -53,28 +62,52 @@ DEV_INLINE unsigned int pp_cvt_pk(float lo, float hi) {
   return r;
 }
 
+typedef __attribute__((ext_vector_type(2))) int pp_int2;
+
+// a staged 8-element chunk as bf16: bf16 chunks as they are
+DEV_INLINE short8 pp_stage_bf16(const short8 x) { return x; }
+
+DEV_INLINE short8 pp_stage_bf16(const pp_int2 x) {
+  typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+  u32x4 w;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float2v lo = __builtin_amdgcn_cvt_pk_f32_fp8(x[i], false);
+    const float2v hi = __builtin_amdgcn_cvt_pk_f32_fp8(x[i], true);
+    w[2 * i] = pp_cvt_pk(lo[0], lo[1]);
+    w[2 * i + 1] = pp_cvt_pk(hi[0], hi[1]);
+  }
+  return __builtin_bit_cast(short8, w);
+}
+
 // WAVES x 32 query rows per block, two waves per SIMD (256 registers a
 // lane): two blocks per CU at 4 waves, one at 8 (64 KB of LDS a block
 // at D = 128), so one wave's staging and softmax overlap another's
 // MFMAs.
-template <int D, int WAVES>
+template <int D, int WAVES, bool FP8>
 __global__ __launch_bounds__(WAVES * 64, 2) void
-paged_attn_prefill_bf16(
+paged_attn_prefill_kernel(
     const short* __restrict__ Q,          // [B, Tq, Hq, D]
-    const short* __restrict__ Kc,         // [num_pages, Hkv, PAGE, D]
-    const short* __restrict__ Vc,
+    const void* __restrict__ Kc_,         // [num_pages, Hkv, PAGE, D]
+    const void* __restrict__ Vc_,
     const int* __restrict__ block_table,  // [B, max_pages]
     const int* __restrict__ ctx_lens,     // [B]
     const int* __restrict__ q_lens,       // [B]
     short* __restrict__ Out,              // [B, Tq, Hq, D]
-    int Tq, int Hq, int Hkv, int num_pages, int max_pages, float scale) {
+    int Tq, int Hq, int Hkv, int num_pages, int max_pages, float scale,
+    float oscale) {
+  // cache element and the 8-element chunk a thread stages
+  typedef std::conditional_t<FP8, unsigned char, short> elem_t;
+  typedef std::conditional_t<FP8, pp_int2, short8> stage_t;
+  const elem_t* Kc = static_cast<const elem_t*>(Kc_);
+  const elem_t* Vc = static_cast<const elem_t*>(Vc_);
   static_assert(D == 64 || D == 128, "head_dim is 64 or 128");
   static_assert(WAVES == 4 || WAVES == 8, "4 or 8 waves per block");
   constexpr int PP_BM = PP_QW * WAVES;   // query rows per block
   constexpr int PP_THREADS = WAVES * 64;
   constexpr int QC = D / 16;   // k-chunks of the S' product
   constexpr int DT = D / 32;   // 32-column tiles of the output
-  constexpr int CPR = D / 8;   // 16-byte chunks per row
+  constexpr int CPR = D / 8;   // 8-element chunks per row
   constexpr int NST = PP_BN * CPR / PP_THREADS;  // staged chunks per thread
   static_assert(PP_BN * CPR % PP_THREADS == 0, "staging must divide evenly");
 
@@ -136,7 +169,7 @@ paged_attn_prefill_bf16(
   const int n_tiles = (k_end + PP_BN - 1) / PP_BN;
 
   const int* bt = block_table + (long long)b * max_pages;
-  short8 k_stage[NST], v_stage[NST];
+  stage_t k_stage[NST], v_stage[NST];
   int pg_stage[NST];  // page ids of this thread's rows, one tile ahead
 
   // Page ids of the rows a thread stages in tile t_idx, clamped into the
@@ -167,7 +200,7 @@ paged_attn_prefill_bf16(
       const int r = i / CPR;                                              \
       const int c = (i % CPR) * 8;                                        \
       const int krow = kt0 + r;                                           \
-      short8 kv{0, 0, 0, 0, 0, 0, 0, 0}, vv{0, 0, 0, 0, 0, 0, 0, 0};      \
+      stage_t kv{}, vv{};                                                 \
       if (krow < k_end) {                                                 \
         const int page =                                                  \
             PREFETCH ? pg_stage[j]                                        \
@@ -175,8 +208,8 @@ paged_attn_prefill_bf16(
         const long long off =                                             \
             (((long long)page * Hkv + hkv) * PP_PAGE + (krow % PP_PAGE)) * \
                 D + c;                                                    \
-        kv = *reinterpret_cast<const short8*>(Kc + off);                  \
-        vv = *reinterpret_cast<const short8*>(Vc + off);                  \
+        kv = *reinterpret_cast<const stage_t*>(Kc + off);                 \
+        vv = *reinterpret_cast<const stage_t*>(Vc + off);                 \
       }                                                                   \
       k_stage[j] = kv;                                                    \
       v_stage[j] = vv;                                                    \
@@ -191,8 +224,9 @@ paged_attn_prefill_bf16(
       const int c = (i % CPR) * 8;                                        \
       /* K swizzled: col_shorts ^= (row&7)<<3 */                          \
       *reinterpret_cast<short8*>(&k_lds[buf][r][c ^ ((r & 7) << 3)]) =    \
-          k_stage[j];                                                     \
-      *reinterpret_cast<short8*>(&v_lds[buf][r][c]) = v_stage[j];         \
+          pp_stage_bf16(k_stage[j]);                                      \
+      *reinterpret_cast<short8*>(&v_lds[buf][r][c]) =                     \
+          pp_stage_bf16(v_stage[j]);                                      \
     }                                                                     \
   } while (0)
 
@@ -340,7 +374,8 @@ paged_attn_prefill_bf16(
 
   // ---- epilogue: O[q][d] = O'[d][q] / l; padded rows are zeros ----
   if (my_q < Tq) {
-    const float inv = (my_q < qlen && l_run > 0.f) ? 1.f / l_run : 0.f;
+    float inv = (my_q < qlen && l_run > 0.f) ? 1.f / l_run : 0.f;
+    if constexpr (FP8) inv *= oscale;
     short* op = Out + my_row;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)

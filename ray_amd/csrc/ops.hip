@@ -175,17 +175,38 @@ at::Tensor gemv(at::Tensor x, at::Tensor w) {
   CHECK_IN(x);                                                          \
   TORCH_CHECK(x.scalar_type() == at::kInt, #x " must be int32")
 
-static void check_paged_cache(const at::Tensor& k_cache,
-                              const at::Tensor& v_cache, int Hkv, int D) {
+// Returns true for an fp8 (OCP e4m3fn) cache, false for bf16. The
+// scales are the pool's static dequantisation factors: value = stored *
+// scale. They only mean something for fp8, so anything but 1 with a
+// bf16 cache is refused.
+static bool check_paged_cache(const at::Tensor& k_cache,
+                              const at::Tensor& v_cache, int Hkv, int D,
+                              double k_scale, double v_scale) {
   CHECK_IN(k_cache); CHECK_IN(v_cache);
-  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16 &&
-              v_cache.scalar_type() == at::kBFloat16,
-              "paged cache must be bf16");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(),
+              "k_cache and v_cache must have the same dtype");
+  const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8 || k_cache.scalar_type() == at::kBFloat16,
+              "paged cache must be bf16 or float8_e4m3fn, got ",
+              k_cache.scalar_type());
+  TORCH_CHECK(std::isfinite(k_scale) && k_scale > 0 &&
+              std::isfinite(v_scale) && v_scale > 0,
+              "paged cache scales must be positive and finite");
+  TORCH_CHECK(fp8 || (k_scale == 1.0 && v_scale == 1.0),
+              "paged cache scales other than 1 need an fp8 cache");
+  // the widest load of an fp8 cache: a decode lane's PA_FP8_EPL bytes
+  // (prefill staging and the appends move 8)
+  if (fp8)
+    TORCH_CHECK(
+        reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % PA_FP8_EPL == 0 &&
+        reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % PA_FP8_EPL == 0,
+        "fp8 paged caches must be ", PA_FP8_EPL, "-byte aligned");
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(),
               "k_cache/v_cache must both be [num_pages, Hkv, 16, D]");
   TORCH_CHECK(k_cache.size(0) >= 1 && k_cache.size(1) == Hkv &&
               k_cache.size(2) == PA_PAGE && k_cache.size(3) == D,
               "paged cache must be [num_pages, Hkv, 16, D] matching q/k");
+  return fp8;
 }
 
 static void launch_paged_reduce(const at::Tensor& ws, at::Tensor& out, int B,
@@ -214,25 +235,28 @@ at::Tensor paged_attn_reduce(at::Tensor workspace, int64_t B, int64_t Hq,
   return out;
 }
 
-template <int D, int REP>
+template <int D, int REP, bool FP8, int EPL>
 static void launch_paged_decode(const at::Tensor& q, const at::Tensor& kc,
                                 const at::Tensor& vc, const at::Tensor& bt,
                                 const at::Tensor& sl, at::Tensor& out,
-                                float* ws_o, float* ws_ml, int S, int Hkv) {
+                                float* ws_o, float* ws_ml, int S, int Hkv,
+                                float k_scale, float v_scale) {
   int B = (int)q.size(0);
-  hipLaunchKernelGGL((paged_attn_decode_bf16<D, REP>), dim3(S, Hkv, B),
-                     dim3(256), 0, cur_stream(), (const short*)q.data_ptr(),
-                     (const short*)kc.data_ptr(), (const short*)vc.data_ptr(),
-                     bt.data_ptr<int>(), sl.data_ptr<int>(),
-                     (short*)out.data_ptr(), ws_o, ws_ml, Hkv,
-                     (int)kc.size(0), (int)bt.size(1),
-                     1.4426950408889634f / sqrtf((float)D));
+  hipLaunchKernelGGL((paged_attn_decode_kernel<D, REP, FP8, EPL>),
+                     dim3(S, Hkv, B), dim3(256), 0, cur_stream(),
+                     (const short*)q.data_ptr(), (const void*)kc.data_ptr(),
+                     (const void*)vc.data_ptr(), bt.data_ptr<int>(),
+                     sl.data_ptr<int>(), (short*)out.data_ptr(), ws_o, ws_ml,
+                     Hkv, (int)kc.size(0), (int)bt.size(1),
+                     1.4426950408889634f / sqrtf((float)D) * k_scale,
+                     v_scale);
 }
 
 at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
                              at::Tensor v_cache, at::Tensor block_table,
                              at::Tensor seq_lens, int64_t num_splits,
-                             c10::optional<at::Tensor> workspace) {
+                             c10::optional<at::Tensor> workspace,
+                             double k_scale, double v_scale) {
   CHECK_IN(q);
   CHECK_I32(block_table);
   CHECK_I32(seq_lens);
@@ -242,7 +266,8 @@ at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
   TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
   TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
   int Hkv = (int)k_cache.size(1);
-  check_paged_cache(k_cache, v_cache, Hkv, D);
+  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
+                                     v_scale);
   TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   int rep = Hq / Hkv;
   TORCH_CHECK(rep == 1 || rep == 2 || rep == 4 || rep == 8,
@@ -275,8 +300,14 @@ at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
     ws_ml = ws_o + (long long)B * Hq * S * D;
   }
 #define PA_LAUNCH(DD, RR)                                                   \
-  launch_paged_decode<DD, RR>(q, k_cache, v_cache, block_table, seq_lens,   \
-                              out, ws_o, ws_ml, S, Hkv)
+  if (fp8)                                                                  \
+    launch_paged_decode<DD, RR, true, PA_FP8_EPL>(                          \
+        q, k_cache, v_cache, block_table, seq_lens, out, ws_o, ws_ml, S,    \
+        Hkv, (float)k_scale, (float)v_scale);                               \
+  else                                                                      \
+    launch_paged_decode<DD, RR, false, 8>(q, k_cache, v_cache, block_table, \
+                                          seq_lens, out, ws_o, ws_ml, S,    \
+                                          Hkv, 1.f, 1.f)
 #define PA_REP(DD)                                                          \
   switch (rep) {                                                            \
     case 1: PA_LAUNCH(DD, 1); break;                                        \
@@ -295,7 +326,8 @@ at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
 // ctx_lens[b] .. ctx_lens[b]+Tq-1, whose own K/V are already appended.
 at::Tensor paged_attn_prefill(at::Tensor q, at::Tensor k_cache,
                               at::Tensor v_cache, at::Tensor block_table,
-                              at::Tensor ctx_lens, at::Tensor q_lens) {
+                              at::Tensor ctx_lens, at::Tensor q_lens,
+                              double k_scale, double v_scale) {
   CHECK_IN(q);
   CHECK_I32(block_table);
   CHECK_I32(ctx_lens);
@@ -308,9 +340,11 @@ at::Tensor paged_attn_prefill(at::Tensor q, at::Tensor k_cache,
   TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
   TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
   int Hkv = (int)k_cache.size(1);
-  check_paged_cache(k_cache, v_cache, Hkv, D);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
-              reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0,
+  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
+                                     v_scale);
+  TORCH_CHECK(fp8 ||
+              (reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0),
               "paged_attn_prefill: caches must be 16-byte aligned");
   TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   int rep = Hq / Hkv;
@@ -336,22 +370,27 @@ at::Tensor paged_attn_prefill(at::Tensor q, at::Tensor k_cache,
   const long long blocks128 = (long long)((Tq + 127) / 128) * Hq * B;
   const int waves = blocks128 >= PP_WIDE_TILE_BLOCKS ? 8 : 4;
   dim3 grid((Tq + 32 * waves - 1) / (32 * waves), Hq, B);
-#define PP_LAUNCH(DD, WW)                                                   \
-  hipLaunchKernelGGL((paged_attn_prefill_bf16<DD, WW>), grid,               \
+#define PP_LAUNCH_T(DD, WW, FP8)                                             \
+  hipLaunchKernelGGL((paged_attn_prefill_kernel<DD, WW, FP8>), grid,        \
                      dim3(64 * WW), 0, cur_stream(),                        \
                      (const short*)q.data_ptr(),                            \
-                     (const short*)k_cache.data_ptr(),                      \
-                     (const short*)v_cache.data_ptr(),                      \
+                     (const void*)k_cache.data_ptr(),                       \
+                     (const void*)v_cache.data_ptr(),                       \
                      block_table.data_ptr<int>(), ctx_lens.data_ptr<int>(), \
                      q_lens.data_ptr<int>(), (short*)out.data_ptr(), Tq,    \
                      Hq, Hkv, (int)k_cache.size(0),                         \
-                     (int)block_table.size(1), 1.0f / sqrtf((float)D))
+                     (int)block_table.size(1),                              \
+                     1.0f / sqrtf((float)D) * (float)k_scale,               \
+                     (float)v_scale)
+#define PP_LAUNCH(DD, WW)                                                   \
+  if (fp8) { PP_LAUNCH_T(DD, WW, true); } else { PP_LAUNCH_T(DD, WW, false); }
   if (D == 64) {
     if (waves == 4) { PP_LAUNCH(64, 4); } else { PP_LAUNCH(64, 8); }
   } else {
     if (waves == 4) { PP_LAUNCH(128, 4); } else { PP_LAUNCH(128, 8); }
   }
 #undef PP_LAUNCH
+#undef PP_LAUNCH_T
   return out;
 }
 
@@ -371,7 +410,8 @@ static long long paged_row_stride(const at::Tensor& t, const char* name) {
 at::Tensor rope_append_paged(at::Tensor q, at::Tensor k, at::Tensor v,
                              at::Tensor cosT, at::Tensor sinT, at::Tensor pos,
                              at::Tensor block_table, at::Tensor k_cache,
-                             at::Tensor v_cache) {
+                             at::Tensor v_cache, double k_scale,
+                             double v_scale) {
   long long q_rs = paged_row_stride(q, "q");
   long long k_rs = paged_row_stride(k, "k");
   long long v_rs = paged_row_stride(v, "v");
@@ -384,7 +424,8 @@ at::Tensor rope_append_paged(at::Tensor q, at::Tensor k, at::Tensor v,
   TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == D &&
               v.size(2) == D && v.size(1) == Hkv,
               "q/k/v shapes disagree");
-  check_paged_cache(k_cache, v_cache, Hkv, D);
+  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
+                                     v_scale);
   TORCH_CHECK(cosT.scalar_type() == at::kFloat &&
               sinT.scalar_type() == at::kFloat && cosT.dim() == 2 &&
               cosT.size(1) == D / 2 && sinT.sizes() == cosT.sizes(),
@@ -395,16 +436,54 @@ at::Tensor rope_append_paged(at::Tensor q, at::Tensor k, at::Tensor v,
               "block_table must be [B, max_pages]");
   auto q_rot = at::empty({B, Hq, D}, q.options());
   if (B == 0) return q_rot;
-  hipLaunchKernelGGL(rope_append_paged_bf16, dim3(B), dim3(256), 0,
-                     cur_stream(), (const short*)q.data_ptr(),
-                     (const short*)k.data_ptr(), (const short*)v.data_ptr(),
-                     q_rs, k_rs, v_rs, cosT.data_ptr<float>(),
-                     sinT.data_ptr<float>(), pos.data_ptr<int>(),
-                     block_table.data_ptr<int>(), (short*)k_cache.data_ptr(),
-                     (short*)v_cache.data_ptr(), (short*)q_rot.data_ptr(), Hq,
-                     Hkv, D, (int)cosT.size(0), (int)k_cache.size(0),
-                     (int)block_table.size(1));
+  // the stored value is x * fp32(1 / scale): the reciprocal is taken
+  // in double and rounded once, as ops.quantize_kv_fp8 does
+#define RA_LAUNCH(FP8)                                                      \
+  hipLaunchKernelGGL(rope_append_paged_kernel<FP8>, dim3(B), dim3(256), 0,  \
+                     cur_stream(), (const short*)q.data_ptr(),              \
+                     (const short*)k.data_ptr(), (const short*)v.data_ptr(),\
+                     q_rs, k_rs, v_rs, cosT.data_ptr<float>(),              \
+                     sinT.data_ptr<float>(), pos.data_ptr<int>(),           \
+                     block_table.data_ptr<int>(), k_cache.data_ptr(),       \
+                     v_cache.data_ptr(), (short*)q_rot.data_ptr(), Hq, Hkv, \
+                     D, (int)cosT.size(0), (int)k_cache.size(0),            \
+                     (int)block_table.size(1), (float)(1.0 / k_scale),      \
+                     (float)(1.0 / v_scale))
+  if (fp8) { RA_LAUNCH(true); } else { RA_LAUNCH(false); }
+#undef RA_LAUNCH
   return q_rot;
+}
+
+// Append T rows of one sequence to its pages: k (already rotated) and v
+// [T, Hkv, D] go to cache rows pos0 .. pos0+T-1 through the sequence's
+// block-table row, quantised when the caches are fp8.
+void kv_append_paged(at::Tensor k, at::Tensor v, int64_t pos0,
+                     at::Tensor block_table_row, at::Tensor k_cache,
+                     at::Tensor v_cache, double k_scale, double v_scale) {
+  long long k_rs = paged_row_stride(k, "k");
+  long long v_rs = paged_row_stride(v, "v");
+  CHECK_I32(block_table_row);
+  int Hkv = (int)k.size(1), D = (int)k.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(v.sizes() == k.sizes(), "k/v shapes disagree");
+  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
+                                     v_scale);
+  TORCH_CHECK(block_table_row.dim() == 1 && block_table_row.size(0) >= 1,
+              "block_table_row must be [max_pages]");
+  TORCH_CHECK(pos0 >= 0 && pos0 < (1ll << 31) && k.size(0) < (1ll << 31),
+              "kv_append_paged: pos0 and T must be in 0..2^31");
+  int T = (int)k.size(0);
+  if (T == 0) return;
+#define KA_LAUNCH(FP8)                                                      \
+  hipLaunchKernelGGL(kv_append_paged_kernel<FP8>, dim3(T), dim3(128), 0,    \
+                     cur_stream(), (const short*)k.data_ptr(),              \
+                     (const short*)v.data_ptr(), k_rs, v_rs,                \
+                     block_table_row.data_ptr<int>(), (int)pos0,            \
+                     k_cache.data_ptr(), v_cache.data_ptr(), Hkv, D,        \
+                     (int)k_cache.size(0), (int)block_table_row.size(0),    \
+                     (float)(1.0 / k_scale), (float)(1.0 / v_scale))
+  if (fp8) { KA_LAUNCH(true); } else { KA_LAUNCH(false); }
+#undef KA_LAUNCH
 }
 
 // ---------------- weight-gradient GEMM ----------------
@@ -758,10 +837,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_attn_decode", &paged_attn_decode, py::arg("q"),
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
         py::arg("seq_lens"), py::arg("num_splits"),
-        py::arg("workspace") = py::none());
+        py::arg("workspace") = py::none(), py::arg("k_scale") = 1.0,
+        py::arg("v_scale") = 1.0);
   m.def("paged_attn_reduce", &paged_attn_reduce);
-  m.def("rope_append_paged", &rope_append_paged);
-  m.def("paged_attn_prefill", &paged_attn_prefill);
+  m.def("rope_append_paged", &rope_append_paged, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("cosT"), py::arg("sinT"), py::arg("pos"),
+        py::arg("block_table"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
+  m.def("kv_append_paged", &kv_append_paged);
+  m.def("paged_attn_prefill", &paged_attn_prefill, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
+        py::arg("ctx_lens"), py::arg("q_lens"), py::arg("k_scale") = 1.0,
+        py::arg("v_scale") = 1.0);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

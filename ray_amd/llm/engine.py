@@ -41,6 +41,22 @@ class LLMConfig:
     # most that many tokens at a time.
     enable_prefix_caching: bool = False
     prefill_chunk_tokens: Optional[int] = None
+    # Paged cache only. kv_cache_dtype: "auto" (the model dtype), "bf16"
+    # or "fp8" ("fp8_e4m3" is the same): fp8 pages hold one byte per
+    # element, K / kv_k_scale and V / kv_v_scale as OCP e4m3fn, so the
+    # same kv_num_pages take half the memory.
+    kv_cache_dtype: str = "auto"
+    kv_k_scale: float = 1.0
+    kv_v_scale: float = 1.0
+
+
+# LLMConfig.kv_cache_dtype -> page dtype (None: the model dtype)
+_KV_CACHE_DTYPES = {
+    "auto": None,
+    "bf16": torch.bfloat16,
+    "fp8": torch.float8_e4m3fn,
+    "fp8_e4m3": torch.float8_e4m3fn,
+}
 
 
 class LLMEngine:
@@ -182,6 +198,13 @@ class ContinuousBatchingEngine:
             raise ValueError(
                 "enable_prefix_caching and prefill_chunk_tokens need "
                 "kv_cache='paged'")
+        if config.kv_cache_dtype not in _KV_CACHE_DTYPES:
+            raise ValueError(
+                f"kv_cache_dtype must be one of {sorted(_KV_CACHE_DTYPES)}, "
+                f"got {config.kv_cache_dtype!r}")
+        kv_dtype = _KV_CACHE_DTYPES[config.kv_cache_dtype]
+        if kv_dtype == torch.float8_e4m3fn and not self._paged:
+            raise ValueError("kv_cache_dtype='fp8' needs kv_cache='paged'")
         if self._paged:
             from ray_amd.llm.paged import PagedDecoder
 
@@ -191,7 +214,10 @@ class ContinuousBatchingEngine:
                                         prefix_caching=(
                                             config.enable_prefix_caching),
                                         prefill_chunk=(
-                                            config.prefill_chunk_tokens))
+                                            config.prefill_chunk_tokens),
+                                        kv_dtype=kv_dtype,
+                                        k_scale=config.kv_k_scale,
+                                        v_scale=config.kv_v_scale)
             if config.use_hip_graph and self.device.type == "cuda":
                 self.decoder.capture()
         else:
@@ -213,6 +239,7 @@ class ContinuousBatchingEngine:
         if self._paged:
             pool = self.decoder.pool
             self.stats["kv_pages_total"] = pool.num_usable
+            self.stats["kv_cache_bytes"] = pool.kv_bytes
             self.stats["kv_pages_free"] = pool.num_free
             self.stats["kv_pages_cached"] = pool.num_cached
             self.stats["prefix_hit_tokens"] = self.decoder.prefix_hit_tokens

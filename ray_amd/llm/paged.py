@@ -37,13 +37,27 @@ class PagedKVPool:
     layer's tensors, so the index is per pool. An indexed page whose
     count drops to 0 keeps its contents and waits in an LRU; alloc takes
     from the free list first and evicts from the LRU only when that is
-    empty. While nothing is registered the pool is a plain free list."""
+    empty. While nothing is registered the pool is a plain free list.
+
+    dtype float8_e4m3fn makes an fp8 pool: a page element is one byte
+    holding value / scale (ops.quantize_kv_fp8), with one static
+    (k_scale, v_scale) pair for the whole pool. Other dtypes store
+    values as they are and take no scale."""
 
     def __init__(self, num_layers: int, num_pages: int, Hkv: int, D: int,
-                 device, dtype=torch.bfloat16, page_size: int = PAGE_SIZE):
+                 device, dtype=torch.bfloat16, page_size: int = PAGE_SIZE,
+                 k_scale: float = 1.0, v_scale: float = 1.0):
         if num_pages < 2:
             raise ValueError("PagedKVPool needs at least 2 pages "
                              "(page 0 is reserved)")
+        if dtype in (torch.float8_e4m3fnuz, torch.float8_e5m2,
+                     torch.float8_e5m2fnuz):
+            raise ValueError(f"fp8 KV pages are float8_e4m3fn, not {dtype}")
+        self.is_fp8 = dtype == torch.float8_e4m3fn
+        self.k_scale = ops._check_kv_scale(k_scale)
+        self.v_scale = ops._check_kv_scale(v_scale)
+        if not self.is_fp8 and (self.k_scale != 1.0 or self.v_scale != 1.0):
+            raise ValueError("KV scales other than 1 need an fp8 pool")
         self.num_pages = num_pages
         self.page_size = page_size
         self.k = [
@@ -61,6 +75,11 @@ class PagedKVPool:
         self._next_node = 1
         # indexed pages with count 0, oldest (first to be evicted) first
         self._lru: "OrderedDict[int, None]" = OrderedDict()
+
+    @property
+    def kv_bytes(self) -> int:
+        """Bytes of K and V pages over all layers."""
+        return sum(t.numel() * t.element_size() for t in self.k + self.v)
 
     @property
     def num_free(self) -> int:
@@ -211,7 +230,9 @@ class PagedDecoder:
     def __init__(self, model, batch_size: int, max_T: int, device,
                  num_pages: Optional[int] = None,
                  prefix_caching: bool = False,
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None,
+                 kv_dtype: Optional[torch.dtype] = None,
+                 k_scale: float = 1.0, v_scale: float = 1.0):
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError("prefill_chunk must be at least 1")
         self.prefix_caching = prefix_caching
@@ -227,8 +248,11 @@ class PagedDecoder:
         self.max_pages = pages_for(max_T)
         if num_pages is None:
             num_pages = batch_size * self.max_pages + 1
+        # kv_dtype None: pages in the model dtype
         self.pool = PagedKVPool(cfg.num_layers, num_pages, cfg.num_kv_heads,
-                                hd, device, model.dtype)
+                                hd, device,
+                                model.dtype if kv_dtype is None else kv_dtype,
+                                k_scale=k_scale, v_scale=v_scale)
         self.block_table = torch.zeros(batch_size, self.max_pages,
                                        dtype=torch.int32, device=device)
         self.seq_lens = torch.zeros(batch_size, dtype=torch.int32,
@@ -299,7 +323,12 @@ class PagedDecoder:
         if n > self.max_T:
             raise ValueError(f"prompt of {n} tokens exceeds max_T "
                              f"{self.max_T}")
-        if self.prefix_caching or self.prefill_chunk is not None:
+        # An fp8 pool always prefills through the pages, so the prompt
+        # attends to the quantised rows that decode will read; the path
+        # below attends to the raw K/V and would give the first token
+        # other keys than every later one.
+        if (self.prefix_caching or self.prefill_chunk is not None
+                or self.pool.is_fp8):
             return self._prefill_slot_paged(slot, toks,
                                             max(reserve_tokens, n))
         self.prefill_tokens_computed += n
@@ -374,9 +403,11 @@ class PagedDecoder:
         dev = self.device
         x = m.embed(toks.view(1, T))
         cos, sin = m.cosT[pos0 : pos0 + T], m.sinT[pos0 : pos0 + T]
-        t = torch.arange(pos0, pos0 + T, device=dev)
-        pg = self.block_table[slot, t // ps].long()
-        sl = t % ps
+        pool = self.pool
+        if not pool.is_fp8:
+            t = torch.arange(pos0, pos0 + T, device=dev)
+            pg = self.block_table[slot, t // ps].long()
+            sl = t % ps
         bt = self.block_table[slot : slot + 1]
         ctx_lens = torch.tensor([pos0], dtype=torch.int32, device=dev)
         q_lens = torch.tensor([T], dtype=torch.int32, device=dev)
@@ -386,11 +417,19 @@ class PagedDecoder:
             q = ops.rope(q, cos, sin)
             k = ops.rope(k, cos, sin)
             kp, vp = self.pool.k[li], self.pool.v[li]
-            # [1,T,Hkv,D] -> rows pos0.. of the slot's pages
-            kp[pg, :, sl] = k[0].to(kp.dtype)
-            vp[pg, :, sl] = v[0].to(vp.dtype)
+            # [1,T,Hkv,D] -> rows pos0.. of the slot's pages. fp8 pages
+            # are written by the append op, so prefill and decode
+            # quantise in one place and shared prefix pages hold the
+            # bytes any request would have produced.
+            if pool.is_fp8:
+                ops.kv_append_paged(k[0], v[0], pos0, bt[0], kp, vp,
+                                    pool.k_scale, pool.v_scale)
+            else:
+                kp[pg, :, sl] = k[0].to(kp.dtype)
+                vp[pg, :, sl] = v[0].to(vp.dtype)
             attn = ops.paged_attention_prefill(q.contiguous(), kp, vp, bt,
-                                               ctx_lens, q_lens)
+                                               ctx_lens, q_lens,
+                                               pool.k_scale, pool.v_scale)
             x = x + at.o_proj(attn.reshape(1, T, -1))
             x = x + layer.mlp(layer.mlp_norm(x))
         if not last:
@@ -411,10 +450,12 @@ class PagedDecoder:
             kp, vp = self.pool.k[li], self.pool.v[li]
             q = ops.rope_append_paged(q[:, 0], k[:, 0], v[:, 0], m.cosT,
                                       m.sinT, self.pos, self.block_table,
-                                      kp, vp)
+                                      kp, vp, self.pool.k_scale,
+                                      self.pool.v_scale)
             attn = ops.paged_attention_decode(
                 q, kp, vp, self.block_table, self.seq_lens,
-                num_splits=self.num_splits, workspace=self.workspace)
+                num_splits=self.num_splits, workspace=self.workspace,
+                k_scale=self.pool.k_scale, v_scale=self.pool.v_scale)
             x = x + lin(attn.reshape(B, 1, -1), at.o_proj.weight)
             hm = layer.mlp_norm(x)
             mp = layer.mlp

@@ -738,13 +738,44 @@ def flash_attention(q, k, v, causal: bool = True, q_offset: int = 0,
 # --------------------------------------------------------------------------
 
 PAGE_SIZE = 16
+FP8_MAX = 448.0  # largest finite float8_e4m3fn
 
 
-def paged_attention_ref(q, k_cache, v_cache, block_table, seq_lens):
+def _check_kv_scale(scale) -> float:
+    scale = float(scale)
+    if not (scale > 0.0 and scale != float("inf")):
+        raise ValueError(f"KV cache scale must be positive and finite, got "
+                         f"{scale!r}")
+    return scale
+
+
+def quantize_kv_fp8(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """The fp8 KV-cache storage rule, in plain torch:
+    e4m3fn_rne(clamp(fp32(x) * fp32(1/scale), -448, 448)). The clamp is
+    explicit and comes first, so nothing depends on how the conversion
+    treats overflow (a bare .to(float8_e4m3fn) gives NaN above 464). The
+    stored value dequantises as stored.float() * scale."""
+    scale = _check_kv_scale(scale)
+    # a 0-d fp32 tensor: the multiply is an fp32 multiply on every backend
+    inv = torch.tensor(1.0 / scale, dtype=torch.float32, device=x.device)
+    y = (x.float() * inv).clamp(-FP8_MAX, FP8_MAX)
+    return y.to(torch.float8_e4m3fn)
+
+
+def _to_kv_cache(x: torch.Tensor, cache: torch.Tensor, scale: float):
+    """x as the elements `cache` stores."""
+    if cache.dtype == torch.float8_e4m3fn:
+        return quantize_kv_fp8(x, scale)
+    return x.to(cache.dtype)
+
+
+def paged_attention_ref(q, k_cache, v_cache, block_table, seq_lens,
+                        k_scale=1.0, v_scale=1.0):
     """fp32 reference. q [B,Hq,D]; k_cache/v_cache
     [num_pages,Hkv,page,D]; block_table [B,max_pages]; seq_lens [B].
     Gathers each row's pages, slices to seq_len, GQA by
-    repeat_interleave. Rows with seq_len 0 give zeros."""
+    repeat_interleave. Rows with seq_len 0 give zeros. Cache values are
+    cache.float() * scale (the fp8 pools' dequantisation)."""
     import math
 
     B, Hq, D = q.shape
@@ -760,8 +791,8 @@ def paged_attention_ref(q, k_cache, v_cache, block_table, seq_lens):
         # [P,Hkv,page,D] -> [Hkv, P*page, D]
         k = k_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :n]
         v = v_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :n]
-        kf = k.float().repeat_interleave(rep, dim=0)
-        vf = v.float().repeat_interleave(rep, dim=0)
+        kf = (k.float() * k_scale).repeat_interleave(rep, dim=0)
+        vf = (v.float() * v_scale).repeat_interleave(rep, dim=0)
         s = torch.einsum("hd,htd->ht", q[b].float(), kf) / math.sqrt(D)
         out[b] = torch.einsum("ht,htd->hd", torch.softmax(s, -1), vf)
     return out.to(q.dtype)
@@ -782,30 +813,35 @@ def default_num_splits(B: int, Hkv: int, max_len: int, device=None) -> int:
 
 
 def paged_attention_decode(q, k_cache, v_cache, block_table, seq_lens,
-                           num_splits=None, workspace=None):
+                           num_splits=None, workspace=None, k_scale=1.0,
+                           v_scale=1.0):
     """Single-token attention over a paged KV cache. q [B,Hq,D] ->
     [B,Hq,D]. num_splits=None picks a value from the block table's
     capacity (no host sync on seq_lens); graph-capturing callers pass a
     fixed value and may pass a static fp32 `workspace` of
-    B*Hq*num_splits*(D+2) elements."""
+    B*Hq*num_splits*(D+2) elements. The caches are bf16, or
+    float8_e4m3fn holding value / scale (see quantize_kv_fp8)."""
     if not q.is_cuda:
         return paged_attention_ref(q, k_cache, v_cache, block_table,
-                                   seq_lens)
+                                   seq_lens, k_scale, v_scale)
     _require_ext("paged_attention_decode")
     if num_splits is None:
         num_splits = default_num_splits(
             q.shape[0], k_cache.shape[1],
             block_table.shape[1] * k_cache.shape[2], q.device)
     return _K.paged_attn_decode(q, k_cache, v_cache, block_table, seq_lens,
-                                int(num_splits), workspace)
+                                int(num_splits), workspace, float(k_scale),
+                                float(v_scale))
 
 
 def rope_append_paged_ref(q, k, v, cosT, sinT, pos, block_table, k_cache,
-                          v_cache):
+                          v_cache, k_scale=1.0, v_scale=1.0):
     """Reference for rope_append_paged: rotate-halves RoPE of q/k at
     each row's own position (fp32 tables), rotated k and raw v written
     in place into page block_table[b, pos//page] slot pos%page; rows
-    with pos < 0 are skipped (zero q_rot). Returns q_rot [B,Hq,D]."""
+    with pos < 0 are skipped (zero q_rot). fp8 caches store
+    quantize_kv_fp8 of the rotated k (rounded to k's dtype first) and of
+    v. Returns q_rot [B,Hq,D]."""
     B, Hq, D = q.shape
     page = k_cache.shape[2]
     q_rot = torch.zeros(B, Hq, D, dtype=q.dtype, device=q.device)
@@ -815,24 +851,59 @@ def rope_append_paged_ref(q, k, v, cosT, sinT, pos, block_table, k_cache,
         c, s = cosT[p : p + 1], sinT[p : p + 1]
         q_rot[b] = rope_ref(q[b].reshape(1, 1, Hq, D), c, s)[0, 0]
         pg = int(block_table[b, p // page])
-        k_cache[pg, :, p % page] = rope_ref(
-            k[b].reshape(1, 1, -1, D), c, s)[0, 0].to(k_cache.dtype)
-        v_cache[pg, :, p % page] = v[b].to(v_cache.dtype)
+        k_cache[pg, :, p % page] = _to_kv_cache(
+            rope_ref(k[b].reshape(1, 1, -1, D), c, s)[0, 0], k_cache, k_scale)
+        v_cache[pg, :, p % page] = _to_kv_cache(v[b], v_cache, v_scale)
     return q_rot
 
 
 def rope_append_paged(q, k, v, cosT, sinT, pos, block_table, k_cache,
-                      v_cache):
+                      v_cache, k_scale=1.0, v_scale=1.0):
     """Fused decode-step RoPE + paged KV append (one launch). q
     [B,Hq,D], k/v [B,Hkv,D] (fused-QKV slices accepted as they are),
     pos [B] int32. Updates k_cache/v_cache in place, returns rotated
     q."""
     if not q.is_cuda:
         return rope_append_paged_ref(q, k, v, cosT, sinT, pos, block_table,
-                                     k_cache, v_cache)
+                                     k_cache, v_cache, k_scale, v_scale)
     _require_ext("rope_append_paged")
     return _K.rope_append_paged(q, k, v, cosT, sinT, pos, block_table,
-                                k_cache, v_cache)
+                                k_cache, v_cache, float(k_scale),
+                                float(v_scale))
+
+
+def kv_append_paged_ref(k, v, pos0, block_table_row, k_cache, v_cache,
+                        k_scale=1.0, v_scale=1.0):
+    """Reference for kv_append_paged: rows k[t], v[t] of [T,Hkv,D] (k
+    already rotated) are written in place to cache row pos0 + t of the
+    pages in block_table_row [max_pages], quantised by quantize_kv_fp8
+    when the cache is fp8. Rows whose page index is past the table, or
+    whose page id is outside the pool, are not written."""
+    page = k_cache.shape[2]
+    num_pages = k_cache.shape[0]
+    table = block_table_row.tolist()
+    for t in range(k.shape[0]):
+        p = int(pos0) + t
+        if p // page >= len(table):
+            continue
+        pg = int(table[p // page])
+        if pg < 0 or pg >= num_pages:
+            continue
+        k_cache[pg, :, p % page] = _to_kv_cache(k[t], k_cache, k_scale)
+        v_cache[pg, :, p % page] = _to_kv_cache(v[t], v_cache, v_scale)
+
+
+def kv_append_paged(k, v, pos0, block_table_row, k_cache, v_cache,
+                    k_scale=1.0, v_scale=1.0):
+    """Append T already-rotated K rows and V rows [T,Hkv,D] of one
+    sequence at cache rows pos0 .. pos0+T-1 (one launch). Updates the
+    caches in place."""
+    if not k.is_cuda:
+        return kv_append_paged_ref(k, v, pos0, block_table_row, k_cache,
+                                   v_cache, k_scale, v_scale)
+    _require_ext("kv_append_paged")
+    _K.kv_append_paged(k, v, int(pos0), block_table_row, k_cache, v_cache,
+                       float(k_scale), float(v_scale))
 
 
 # --------------------------------------------------------------------------
@@ -841,7 +912,7 @@ def rope_append_paged(q, k, v, cosT, sinT, pos, block_table, k_cache,
 
 
 def paged_attention_prefill_ref(q, k_cache, v_cache, block_table, ctx_lens,
-                                q_lens):
+                                q_lens, k_scale=1.0, v_scale=1.0):
     """fp32 reference. q [B,Tq,Hq,D] is a chunk of queries at positions
     ctx_lens[b] .. ctx_lens[b]+Tq-1 whose own K/V are already in the
     pages. Gathers each row's pages as paged_attention_ref does, then
@@ -863,8 +934,8 @@ def paged_attention_prefill_ref(q, k_cache, v_cache, block_table, ctx_lens,
         # [P,Hkv,page,D] -> [Hkv, P*page, D]
         k = k_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :L]
         v = v_cache[pages].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, :L]
-        kf = k.float().repeat_interleave(rep, dim=0)
-        vf = v.float().repeat_interleave(rep, dim=0)
+        kf = (k.float() * k_scale).repeat_interleave(rep, dim=0)
+        vf = (v.float() * v_scale).repeat_interleave(rep, dim=0)
         s = torch.einsum("thd,hjd->htj", q[b, :n].float(), kf) / math.sqrt(D)
         i = torch.arange(n, device=q.device).view(n, 1)
         j = torch.arange(L, device=q.device).view(1, L)
@@ -874,14 +945,14 @@ def paged_attention_prefill_ref(q, k_cache, v_cache, block_table, ctx_lens,
 
 
 def paged_attention_prefill(q, k_cache, v_cache, block_table, ctx_lens,
-                            q_lens):
+                            q_lens, k_scale=1.0, v_scale=1.0):
     """Causal attention from a chunk of query tokens to a paged KV
     cache. q [B,Tq,Hq,D] bf16 contiguous -> [B,Tq,Hq,D]; ctx_lens [B]
     int32 rows cached before the chunk, q_lens [B] int32 valid query
     rows. The chunk's K/V must already be appended to the pages."""
     if not q.is_cuda:
         return paged_attention_prefill_ref(q, k_cache, v_cache, block_table,
-                                           ctx_lens, q_lens)
+                                           ctx_lens, q_lens, k_scale, v_scale)
     _require_ext("paged_attention_prefill")
     return _K.paged_attn_prefill(q, k_cache, v_cache, block_table, ctx_lens,
-                                 q_lens)
+                                 q_lens, float(k_scale), float(v_scale))

@@ -3,11 +3,12 @@
 
     python tools/decode_bench.py [--model llama3-8b] [--tokens 128]
                                  [--ctx N[,N...]] [--paged] [--reps R]
+                                 [--kv-dtype bf16,fp8]
 
 --ctx N starts decoding at context length N (default 64, i.e. tokens
 64..72+tokens); --paged adds a row per batch for the graph-captured
 PagedDecoder (paged KV cache + fused decode attention) at the same
-positions.
+positions, once per --kv-dtype (fp8: one-byte OCP e4m3fn pages).
 """
 import argparse
 import os
@@ -71,7 +72,11 @@ def main():
     ap.add_argument("--reps", type=int, default=1,
                     help="timed repetitions of each captured row; the row "
                          "shows the median and [min, max] ms/step")
+    ap.add_argument("--kv-dtype", default="bf16",
+                    help="--paged cache formats, comma-separated: bf16, fp8")
     args = ap.parse_args()
+    kv_dtypes = args.kv_dtype.split(",")
+    assert set(kv_dtypes) <= {"bf16", "fp8"}, kv_dtypes
 
     dev = torch.device("cuda", 0)
     cfg = CONFIGS[args.model]
@@ -105,21 +110,27 @@ def main():
                 continue
             from ray_amd.llm.paged import PagedDecoder
 
-            pd = PagedDecoder(model, B, max_T, dev)
-            for k, v in zip(pd.pool.k, pd.pool.v):
-                k.zero_()  # like the contiguous decoders' zero caches
-                v.zero_()
-            for slot in range(B):
-                pd.reserve_slot(slot, max_T)
-            pd.capture()
-            pms, pspread = timed(
-                lambda: bench_paged(pd, cfg, B, args.tokens, ctx))
-            print(f"batch {B:3d}: paged hipGraph "
-                  f"{B / pms * 1e3:9.1f} tok/s "
-                  f"({pms:6.2f} ms/step{pspread})   "
-                  f"splits {pd.num_splits}  "
-                  f"GraphedDecoder/paged {ms / pms:5.2f}x")
-            del pd
+            for kv_dtype in kv_dtypes:
+                pd = PagedDecoder(
+                    model, B, max_T, dev,
+                    kv_dtype=torch.float8_e4m3fn if kv_dtype == "fp8"
+                    else None)
+                for k, v in zip(pd.pool.k, pd.pool.v):
+                    # like the contiguous decoders' zero caches
+                    k.view(torch.uint8).zero_()
+                    v.view(torch.uint8).zero_()
+                for slot in range(B):
+                    pd.reserve_slot(slot, max_T)
+                pd.capture()
+                pms, pspread = timed(
+                    lambda: bench_paged(pd, cfg, B, args.tokens, ctx))
+                name = "paged" if kv_dtype == "bf16" else "paged fp8"
+                print(f"batch {B:3d}: {name} hipGraph "
+                      f"{B / pms * 1e3:9.1f} tok/s "
+                      f"({pms:6.2f} ms/step{pspread})   "
+                      f"splits {pd.num_splits}  "
+                      f"GraphedDecoder/paged {ms / pms:5.2f}x")
+                del pd
 
 
 if __name__ == "__main__":

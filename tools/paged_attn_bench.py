@@ -3,10 +3,13 @@ do today: F.scaled_dot_product_attention with an additive mask over an
 equally sized contiguous [B, Hkv, capacity, D] cache.
 
     python tools/paged_attn_bench.py [--batches 1,8,32] [--lens 1024,4096]
+        [--kv-dtype bf16,fp8]
 
 Reports median / min / max microseconds per call over --reps timed
 repetitions (each of --iters back-to-back calls, after warm-up) and
-the achieved KV read rate 2*B*Hkv*seq_len*D*2 bytes per call.
+the achieved KV read rate 2*B*Hkv*seq_len*D*(bytes per cache element)
+per call. With an fp8 cache the reference reads the dequantised values
+as bf16 (exact), so max|diff| is kernel arithmetic alone.
 """
 import argparse
 import os
@@ -52,7 +55,11 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--splits", type=int, default=0,
                     help="0 = the op's default choice")
+    ap.add_argument("--kv-dtype", default="bf16",
+                    help="comma-separated cache formats: bf16, fp8")
     args = ap.parse_args()
+    kv_dtypes = args.kv_dtype.split(",")
+    assert set(kv_dtypes) <= {"bf16", "fp8"}, kv_dtypes
 
     dev = torch.device("cuda", 0)
     Hq, Hkv, D, cap = args.hq, args.hkv, args.d, args.capacity
@@ -61,20 +68,25 @@ def main():
     torch.manual_seed(0)
     print(f"# Hq={Hq} Hkv={Hkv} D={D} capacity={cap} iters={args.iters} "
           f"reps={args.reps}; us per call: median [min, max]")
-    for B in [int(b) for b in args.batches.split(",")]:
+    for kv_dtype, B in [(k, int(b)) for k in kv_dtypes
+                        for b in args.batches.split(",")]:
+        if args.kv_dtype != "bf16":
+            print(f"# kv_dtype={kv_dtype}")
         num_pages = B * max_pages + 1
         kc = torch.randn(num_pages, Hkv, page, D, device=dev,
                          dtype=torch.bfloat16)
         vc = torch.randn_like(kc)
+        if kv_dtype == "fp8":
+            kc, vc = ops.quantize_kv_fp8(kc), ops.quantize_kv_fp8(vc)
         # shuffled page assignment, as a long-running pool would have
         perm = (torch.randperm(num_pages - 1) + 1).to(torch.int32)
         bt = perm.view(B, max_pages).to(dev)
         q = torch.randn(B, Hq, D, device=dev, dtype=torch.bfloat16)
         # the same K/V, contiguous, for the reference
         ck = (kc[bt.long()].permute(0, 2, 1, 3, 4)
-              .reshape(B, Hkv, cap, D).contiguous())
+              .reshape(B, Hkv, cap, D).contiguous().to(torch.bfloat16))
         cv = (vc[bt.long()].permute(0, 2, 1, 3, 4)
-              .reshape(B, Hkv, cap, D).contiguous())
+              .reshape(B, Hkv, cap, D).contiguous().to(torch.bfloat16))
         q4 = q.view(B, Hq, 1, D)
         for L in [int(x) for x in args.lens.split(",")]:
             sl = torch.full((B,), L, dtype=torch.int32, device=dev)
@@ -98,7 +110,7 @@ def main():
                          - sdpa().view(B, Hq, D).float()).abs().max())
             p_med, p_min, p_max = time_us(paged, args.iters, args.reps)
             s_med, s_min, s_max = time_us(sdpa, args.iters, args.reps)
-            kv_bytes = 2 * B * Hkv * L * D * 2
+            kv_bytes = 2 * B * Hkv * L * D * kc.element_size()
             tbs = kv_bytes / (p_med * 1e-6) / 1e12
             print(f"B={B:3d} seq_len={L:5d} splits={S:3d}  "
                   f"paged {p_med:8.1f} [{p_min:8.1f},{p_max:8.1f}] us "

@@ -5,6 +5,7 @@ for a shared prefix plus a tail, cold and warm.
 
     python tools/paged_prefill_bench.py [--shapes 3072:1024,0:4096]
         [--model llama3-8b] [--prefix 2048] [--tail 128] [--skip-model]
+        [--kv-dtype bf16,fp8]
 
 (a) reports median [min, max] microseconds per call over --reps timed
 repetitions of --iters back-to-back calls after warm-up, and the
@@ -12,6 +13,9 @@ achieved rate on the causal FLOPs 4*Hq*D*(visible q-k pairs).
 (b) reports median [min, max] milliseconds per prefill_slot call over
 --reps prompts; every prompt has a fresh random prefix, prefilled once
 cold and once more (with another tail) warm.
+With --kv-dtype fp8 the kernel rows run on an fp8 cache (the composite
+reads the dequantised values as bf16, which is exact), and the model
+rows are cold and warm prefill into an fp8 pool.
 """
 import argparse
 import os
@@ -42,11 +46,12 @@ def time_us(fn, iters, reps, warmup=5):
     return statistics.median(out), min(out), max(out)
 
 
-def bench_kernel(args, dev):
+def bench_kernel(args, dev, kv_dtype):
     Hq, Hkv, D = args.hq, args.hkv, args.d
     page = ops.PAGE_SIZE
+    tag = "" if kv_dtype == "bf16" else f" kv_dtype={kv_dtype}"
     print(f"# (a) kernel: Hq={Hq} Hkv={Hkv} D={D} B=1 iters={args.iters} "
-          f"reps={args.reps}; us per call: median [min, max]")
+          f"reps={args.reps}{tag}; us per call: median [min, max]")
     for spec in args.shapes.split(","):
         ctx, Tq = (int(x) for x in spec.split(":"))
         L = ctx + Tq
@@ -56,6 +61,8 @@ def bench_kernel(args, dev):
         kc = torch.randn(num_pages, Hkv, page, D, device=dev,
                          dtype=torch.bfloat16)
         vc = torch.randn_like(kc)
+        if kv_dtype == "fp8":
+            kc, vc = ops.quantize_kv_fp8(kc), ops.quantize_kv_fp8(vc)
         # shuffled page assignment, as a long-running pool would have
         bt = (torch.randperm(num_pages - 1) + 1).to(torch.int32).view(
             1, n_pages).to(dev)
@@ -72,6 +79,8 @@ def bench_kernel(args, dev):
             # the layout flash_attention takes without another copy
             k = kc[pages].permute(0, 2, 1, 3).reshape(1, -1, Hkv, D)[:, :L]
             v = vc[pages].permute(0, 2, 1, 3).reshape(1, -1, Hkv, D)[:, :L]
+            if kv_dtype == "fp8":
+                k, v = k.to(torch.bfloat16), v.to(torch.bfloat16)
             o = ops.flash_attention(q.transpose(1, 2), k.transpose(1, 2),
                                     v.transpose(1, 2), causal=True,
                                     q_offset=ctx)
@@ -91,7 +100,44 @@ def bench_kernel(args, dev):
         del kc, vc
 
 
-def bench_model(args, dev):
+def bench_model_fp8(args, dev, model):
+    """Cold and warm prefill_slot into an fp8 pool."""
+    from ray_amd.llm.paged import PagedDecoder
+
+    cfg = model.cfg
+    n = args.prefix + args.tail
+    print(f"# (b) {args.model} prefill_slot, kv_dtype=fp8: prefix "
+          f"{args.prefix} + tail {args.tail} tokens, reps={args.reps}; ms "
+          f"per call: median [min, max]")
+    cached = PagedDecoder(model, 1, n + 64, dev, prefix_caching=True,
+                          kv_dtype=torch.float8_e4m3fn)
+    rows = {"cold": [], "warm": []}
+
+    def once(prefix):
+        tail = torch.randint(0, cfg.vocab_size, (args.tail,), device=dev)
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        cached.prefill_slot(0, torch.cat([prefix, tail]))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    with torch.no_grad():
+        for rep in range(args.reps + 1):  # rep 0 warms both paths up
+            prefix = torch.randint(0, cfg.vocab_size, (args.prefix,),
+                                   device=dev)
+            t = [once(prefix), once(prefix)]
+            if rep:
+                for ms, v in zip(rows.values(), t):
+                    ms.append(v)
+    for name, ms in rows.items():
+        print(f"{name:32s} {statistics.median(ms):8.2f} [{min(ms):8.2f},"
+              f"{max(ms):8.2f}] ms")
+
+
+def bench_model(args, dev, kv_dtypes):
     from ray_amd.llm.paged import PagedDecoder
     from ray_amd.models.llama import CONFIGS, LlamaModel
 
@@ -101,6 +147,8 @@ def bench_model(args, dev):
         model = LlamaModel(cfg, dtype=torch.bfloat16).eval()
     model.cosT = model.cosT.to(dev)
     model.sinT = model.sinT.to(dev)
+    if "bf16" not in kv_dtypes:
+        return bench_model_fp8(args, dev, model)
     n = args.prefix + args.tail
     max_T = n + 64
     print(f"# (b) {args.model} prefill_slot: prefix {args.prefix} + tail "
@@ -152,6 +200,9 @@ def bench_model(args, dev):
     cold, warm = (statistics.median(rows[k]) for k in ("cold", "warm"))
     print(f"warm computes {n - args.prefix // 16 * 16} of {n} tokens: "
           f"cold/warm {cold / warm:5.2f}x")
+    if "fp8" in kv_dtypes:
+        del plain, cached, chunked
+        bench_model_fp8(args, dev, model)
 
 
 def main():
@@ -168,12 +219,17 @@ def main():
     ap.add_argument("--tail", type=int, default=128)
     ap.add_argument("--chunk", type=int, default=512)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--kv-dtype", default="bf16",
+                    help="comma-separated cache formats: bf16, fp8")
     args = ap.parse_args()
+    kv_dtypes = args.kv_dtype.split(",")
+    assert set(kv_dtypes) <= {"bf16", "fp8"}, kv_dtypes
     assert torch.cuda.is_available(), "paged_prefill_bench needs a GPU"
     dev = torch.device("cuda", 0)
-    bench_kernel(args, dev)
+    for kv_dtype in kv_dtypes:
+        bench_kernel(args, dev, kv_dtype)
     if not args.skip_model:
-        bench_model(args, dev)
+        bench_model(args, dev, kv_dtypes)
 
 
 if __name__ == "__main__":
