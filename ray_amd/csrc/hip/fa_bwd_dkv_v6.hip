@@ -71,11 +71,11 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
 
   // K register-resident (B operand of S: lane = key, 8 d per k-step half);
   // V into LDS once.
-  fb3_bf16x8 k_frag[8];
+  bf16x8 k_frag[8];
   {
     const short* kp = K + kbase + ((long long)32 * wave + (lane & 31)) * kv_rs;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) k_frag[c] = fb3_ld8(kp + 16 * c + 8 * hi);
+    for (int c = 0; c < 8; ++c) k_frag[c] = ld8(kp + 16 * c + 8 * hi);
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -87,11 +87,11 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
                                          8 * c);
   }
 
-  fb3_f32x16 dk_acc[4], dv_acc[4];
+  f32x16 dk_acc[4], dv_acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    dk_acc[t] = fb3_f32x16{};
-    dv_acc[t] = fb3_f32x16{};
+    dk_acc[t] = f32x16{};
+    dv_acc[t] = f32x16{};
   }
   const float c2 = scale * 1.4426950408889634f;
 
@@ -191,7 +191,7 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
       if (causal && k0 + 32 * wave > qts + 31) continue;
 
       // S' = Q·K^T - LSE/scale and dP' = dO·V^T - delta, key on the lane
-      fb3_f32x16 s_acc, dp_acc;
+      f32x16 s_acc, dp_acc;
       {
         const float* lp = lse_lds + cur * FB3_QT + 32 * qt + 4 * hi;
         const float* dp = dsum_lds + cur * FB3_QT + 32 * qt + 4 * hi;
@@ -210,9 +210,9 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           const int o = ((c & 1) ? rb1 : rb0) + 256 * (c >> 1) + 4096 * qt;
-          fb3_bf16x8 qf = fb3_ld8(q_lds + o);
-          fb3_bf16x8 dof = fb3_ld8(do_lds + o);
-          fb3_bf16x8 vf = fb3_ld8(((c & 1) ? vw1 : vw0) + 256 * (c >> 1));
+          bf16x8 qf = ld8(q_lds + o);
+          bf16x8 dof = ld8(do_lds + o);
+          bf16x8 vf = ld8(((c & 1) ? vw1 : vw0) + 256 * (c >> 1));
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, k_frag[c],
                                                           s_acc, 0, 0, 0);
           dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vf, dp_acc,
@@ -231,19 +231,19 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
         s_acc[r] = pv;
         dp_acc[r] = pv * dp_acc[r] * scale;
       }
-      fb3_bf16x8 p_frag[2], ds_frag[2];
+      bf16x8 p_frag[2], ds_frag[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        fb6_u32x4 pw{fb6_cvt_pk(s_acc[8 * s + 0], s_acc[8 * s + 1]),
-                     fb6_cvt_pk(s_acc[8 * s + 2], s_acc[8 * s + 3]),
-                     fb6_cvt_pk(s_acc[8 * s + 4], s_acc[8 * s + 5]),
-                     fb6_cvt_pk(s_acc[8 * s + 6], s_acc[8 * s + 7])};
-        fb6_u32x4 dw{fb6_cvt_pk(dp_acc[8 * s + 0], dp_acc[8 * s + 1]),
-                     fb6_cvt_pk(dp_acc[8 * s + 2], dp_acc[8 * s + 3]),
-                     fb6_cvt_pk(dp_acc[8 * s + 4], dp_acc[8 * s + 5]),
-                     fb6_cvt_pk(dp_acc[8 * s + 6], dp_acc[8 * s + 7])};
-        p_frag[s] = __builtin_bit_cast(fb3_bf16x8, pw);
-        ds_frag[s] = __builtin_bit_cast(fb3_bf16x8, dw);
+        u32x4 pw{cvt_pk(s_acc[8 * s + 0], s_acc[8 * s + 1]),
+                     cvt_pk(s_acc[8 * s + 2], s_acc[8 * s + 3]),
+                     cvt_pk(s_acc[8 * s + 4], s_acc[8 * s + 5]),
+                     cvt_pk(s_acc[8 * s + 6], s_acc[8 * s + 7])};
+        u32x4 dw{cvt_pk(dp_acc[8 * s + 0], dp_acc[8 * s + 1]),
+                     cvt_pk(dp_acc[8 * s + 2], dp_acc[8 * s + 3]),
+                     cvt_pk(dp_acc[8 * s + 4], dp_acc[8 * s + 5]),
+                     cvt_pk(dp_acc[8 * s + 6], dp_acc[8 * s + 7])};
+        p_frag[s] = __builtin_bit_cast(bf16x8, pw);
+        ds_frag[s] = __builtin_bit_cast(bf16x8, dw);
       }
 
       // dV^T += dO^T·P and dK^T += Q^T·dS: A via ds_read_tr16_b64 in the
@@ -268,10 +268,10 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
               qtmp[4 * h + j] = q4[j];
             }
           }
-          fb3_bf16x8 adO = __builtin_bit_cast(
-              fb3_bf16x8, *reinterpret_cast<short8*>(dtmp));
-          fb3_bf16x8 aQ = __builtin_bit_cast(
-              fb3_bf16x8, *reinterpret_cast<short8*>(qtmp));
+          bf16x8 adO = __builtin_bit_cast(
+              bf16x8, *reinterpret_cast<short8*>(dtmp));
+          bf16x8 aQ = __builtin_bit_cast(
+              bf16x8, *reinterpret_cast<short8*>(qtmp));
           dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               adO, p_frag[s], dv_acc[dt], 0, 0, 0);
           dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
@@ -309,10 +309,10 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const fb3_f32x16& a = pass == 0 ? dk_acc[dt] : dv_acc[dt];
-        fb6_u32x2 w{fb6_cvt_pk(a[4 * g + 0], a[4 * g + 1]),
-                    fb6_cvt_pk(a[4 * g + 2], a[4 * g + 3])};
-        *reinterpret_cast<fb6_u32x2*>(ep + er * FB6_EP_STRIDE + 32 * dt +
+        const f32x16& a = pass == 0 ? dk_acc[dt] : dv_acc[dt];
+        u32x2 w{cvt_pk(a[4 * g + 0], a[4 * g + 1]),
+                    cvt_pk(a[4 * g + 2], a[4 * g + 3])};
+        *reinterpret_cast<u32x2*>(ep + er * FB6_EP_STRIDE + 32 * dt +
                                       8 * g + 4 * eh) = w;
       }
 #pragma unroll

@@ -46,23 +46,23 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
            : (((long long)b * Hkv + hkv) * T) * FB3_D;
   const int my_q = q0 + wave * 32 + (lane & 31);
 
-  fb3_bf16x8 q_frag[8], do_frag[8];
+  bf16x8 q_frag[8], do_frag[8];
   {
     const short* qp = Q + qbase + ((long long)wave * 32 + (lane & 31)) * q_rs;
     const short* dp = dO + qbase + ((long long)wave * 32 + (lane & 31)) * q_rs;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      q_frag[c] = fb3_ld8(qp + 16 * c + 8 * hi);
-      do_frag[c] = fb3_ld8(dp + 16 * c + 8 * hi);
+      q_frag[c] = ld8(qp + 16 * c + 8 * hi);
+      do_frag[c] = ld8(dp + 16 * c + 8 * hi);
     }
   }
   const float c2 = scale * 1.4426950408889634f;
   float s_init = -LSE[((long long)b * Hq + hq) * T + my_q] / scale;
   float dp_init = -Dsum[((long long)b * Hq + hq) * T + my_q];
 
-  fb3_f32x16 dq_acc[4];
+  f32x16 dq_acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dq_acc[t] = fb3_f32x16{};
+  for (int t = 0; t < 4; ++t) dq_acc[t] = f32x16{};
 
   const int wave_k_max = q0 + wave * 32 + 31;  // last k this wave needs
   const int k_end = causal ? min(T, q0 + 256) : T;
@@ -126,7 +126,7 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
 
       // S'^T = K·Q^T - LSE/scale and dP'^T = V·dO^T - delta ([k][q], the
       // lane owns column q)
-      fb3_f32x16 s_acc, dp_acc;
+      f32x16 s_acc, dp_acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         s_acc[r] = s_init;
@@ -136,8 +136,8 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           const int o = ((c & 1) ? rb1 : rb0) + 256 * (c >> 1) + 4096 * kt;
-          fb3_bf16x8 kf = fb3_ld8(kbuf + o);
-          fb3_bf16x8 vf = fb3_ld8(vbuf + o);
+          bf16x8 kf = ld8(kbuf + o);
+          bf16x8 vf = ld8(vbuf + o);
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, q_frag[c],
                                                           s_acc, 0, 0, 0);
           dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, do_frag[c],
@@ -159,15 +159,15 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
       // ds_read_tr16_b64
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const unsigned int a0 = fb6_cvt_pk(ds[8 * s + 0], ds[8 * s + 1]);
-        const unsigned int a1 = fb6_cvt_pk(ds[8 * s + 2], ds[8 * s + 3]);
-        const unsigned int b0 = fb6_cvt_pk(ds[8 * s + 4], ds[8 * s + 5]);
-        const unsigned int b1 = fb6_cvt_pk(ds[8 * s + 6], ds[8 * s + 7]);
+        const unsigned int a0 = cvt_pk(ds[8 * s + 0], ds[8 * s + 1]);
+        const unsigned int a1 = cvt_pk(ds[8 * s + 2], ds[8 * s + 3]);
+        const unsigned int b0 = cvt_pk(ds[8 * s + 4], ds[8 * s + 5]);
+        const unsigned int b1 = cvt_pk(ds[8 * s + 6], ds[8 * s + 7]);
         auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        fb6_u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
+        u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
                      (unsigned)sw1[1]};
-        const fb3_bf16x8 af = __builtin_bit_cast(fb3_bf16x8, pw);
+        const bf16x8 af = __builtin_bit_cast(bf16x8, pw);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           short ktmp[8];
@@ -182,8 +182,8 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
 #pragma unroll
             for (int j = 0; j < 4; ++j) ktmp[4 * h + j] = r4[j];
           }
-          fb3_bf16x8 bf = __builtin_bit_cast(
-              fb3_bf16x8, *reinterpret_cast<short8*>(ktmp));
+          bf16x8 bf = __builtin_bit_cast(
+              bf16x8, *reinterpret_cast<short8*>(ktmp));
           dq_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               af, bf, dq_acc[dt], 0, 0, 0);
         }

@@ -1,5 +1,5 @@
-// LDS tile image, address helpers and small conversions shared by the
-// key-on-lane dK/dV kernel (fa_bwd_dkv_v6.hip) and dq v5 (fa_bwd_dq_v5.hip).
+// LDS tile image and address helpers shared by the key-on-lane dK/dV
+// kernel (fa_bwd_dkv_v6.hip), dq v5 (fa_bwd_dq_v5.hip) and gemm_wgrad.hip.
 #pragma once
 #include "common.h"
 
@@ -36,19 +36,3 @@ DEV_INLINE int fb6_lane_fresh() {
       : "=v"(l));
   return l;
 }
-
-// Two f32 -> packed bf16 (round to nearest even) as a plain cast, which
-// hipcc lowers to v_cvt_pk_bf16_f32 and schedules like any VALU write.
-// The inline-asm fb3_cvt_pk of fa_bwd_v3.hip is not used here: with its
-// result as the A operand of the very next MFMA, dQ came out wrong in the 32
-// columns of that first MFMA (measured; PERFORMANCE.md, backward ladder,
-// "cvt_pk"), which is what a missing VALU-write -> MFMA-read wait state
-// looks like. dq v3 is unaffected: a permlane32_swap sits in between.
-typedef __attribute__((ext_vector_type(2))) __bf16 fb6_bf16x2;
-DEV_INLINE unsigned int fb6_cvt_pk(float lo, float hi) {
-  fb6_bf16x2 v{(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned int, v);
-}
-
-typedef __attribute__((ext_vector_type(4))) unsigned int fb6_u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int fb6_u32x2;

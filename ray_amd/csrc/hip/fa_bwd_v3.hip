@@ -15,10 +15,7 @@
 // dV += P^T·dO and dK += dS̃^T·Q need a true 32x32 lane transpose, done
 // through a per-wave padded LDS scratch tile.
 //
-// Layout cheatsheet (fa_probe32-verified, 32x32x16):
-//   A (32x16) row-major: lane l holds A[l&31][8*(l>>5)+i]
-//   B (16x32):           lane l holds B[8*(l>>5)+i][l&31]
-//   C:                   col=lane&31, row=(r&3)+8*(r>>2)+4*(l>>5)
+// The MFMA lane layouts are in fa_tile.h.
 #include "fa_bwd_frag.h"
 
 // ---------------------------------------------------------------------
@@ -47,16 +44,16 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
 
   const long long kbase = (((long long)b * Hkv + hkv) * T + k0) * FB3_D;
   // K register-resident: only this wave's own 32 rows are ever read
-  fb3_bf16x8 k_frag[8];
+  bf16x8 k_frag[8];
   {
     const short* kp = K + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) k_frag[c] = fb3_ld8(kp + 16 * c + a_off);
+    for (int c = 0; c < 8; ++c) k_frag[c] = ld8(kp + 16 * c + a_off);
   }
 
-  fb3_f32x16 dv_acc[4];
+  f32x16 dv_acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dv_acc[t] = fb3_f32x16{};
+  for (int t = 0; t < 4; ++t) dv_acc[t] = f32x16{};
   const float L2E = 1.4426950408889634f;
 
   const int q_start = causal ? k0 : 0;
@@ -123,7 +120,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
       if (qts >= T) break;
       if (causal && k0 + 32 * wave > qts + 31) continue;
 
-      fb3_f32x16 s_acc{};
+      f32x16 s_acc{};
       {
         const int rr = 32 * qt + (lane & 31);
         const short* qrow = &q_lds[cur][rr][0];
@@ -131,7 +128,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
           // S'^T tile: A = this wave's K rows (regs), B = Q^T from LDS
-          fb3_bf16x8 qf = fb3_ld8(qrow + ((16 * c + a_off) ^ sw));
+          bf16x8 qf = ld8(qrow + ((16 * c + a_off) ^ sw));
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_frag[c], qf,
                                                           s_acc, 0, 0, 0);
         }
@@ -153,8 +150,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
       __builtin_amdgcn_s_waitcnt(0);
 #pragma unroll
       for (int qc = 0; qc < 2; ++qc) {
-        fb3_bf16x8 af = __builtin_bit_cast(
-            fb3_bf16x8, *reinterpret_cast<const short8*>(
+        bf16x8 af = __builtin_bit_cast(
+            bf16x8, *reinterpret_cast<const short8*>(
                             &scr[lane & 31][16 * qc + a_off]));
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
@@ -165,8 +162,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
             int col = 32 * dt + (lane & 31);
             dtmp[i] = do_lds[cur][row][col ^ ((row & 7) << 3)];
           }
-          fb3_bf16x8 bf = __builtin_bit_cast(
-              fb3_bf16x8, *reinterpret_cast<short8*>(dtmp));
+          bf16x8 bf = __builtin_bit_cast(
+              bf16x8, *reinterpret_cast<short8*>(dtmp));
           dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               af, bf, dv_acc[dt], 0, 0, 0);
         }
@@ -215,20 +212,20 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
   const int a_off = 8 * hi;
 
   const long long kbase = (((long long)b * Hkv + hkv) * T + k0) * FB3_D;
-  fb3_bf16x8 k_frag[8], v_frag[8];
+  bf16x8 k_frag[8], v_frag[8];
   {
     const short* kp = K + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
     const short* vp = V + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      k_frag[c] = fb3_ld8(kp + 16 * c + a_off);
-      v_frag[c] = fb3_ld8(vp + 16 * c + a_off);
+      k_frag[c] = ld8(kp + 16 * c + a_off);
+      v_frag[c] = ld8(vp + 16 * c + a_off);
     }
   }
 
-  fb3_f32x16 dk_acc[4];
+  f32x16 dk_acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dk_acc[t] = fb3_f32x16{};
+  for (int t = 0; t < 4; ++t) dk_acc[t] = f32x16{};
   const float L2E = 1.4426950408889634f;
 
   const int q_start = causal ? k0 : 0;
@@ -284,7 +281,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
       if (qts >= T) break;
       if (causal && k0 + 32 * wave > qts + 31) continue;
 
-      fb3_f32x16 s_acc{}, dp_acc{};
+      f32x16 s_acc{}, dp_acc{};
       {
         const int rr = 32 * qt + (lane & 31);
         const short* qrow = &q_lds[cur][rr][0];
@@ -292,8 +289,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
         const int sw = (rr & 7) << 3;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          fb3_bf16x8 qf = fb3_ld8(qrow + ((16 * c + a_off) ^ sw));
-          fb3_bf16x8 dof = fb3_ld8(dorow + ((16 * c + a_off) ^ sw));
+          bf16x8 qf = ld8(qrow + ((16 * c + a_off) ^ sw));
+          bf16x8 dof = ld8(dorow + ((16 * c + a_off) ^ sw));
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_frag[c], qf,
                                                           s_acc, 0, 0, 0);
           dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_frag[c], dof,
@@ -317,8 +314,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
       __builtin_amdgcn_s_waitcnt(0);
 #pragma unroll
       for (int qc = 0; qc < 2; ++qc) {
-        fb3_bf16x8 af = __builtin_bit_cast(
-            fb3_bf16x8, *reinterpret_cast<const short8*>(
+        bf16x8 af = __builtin_bit_cast(
+            bf16x8, *reinterpret_cast<const short8*>(
                             &scr[lane & 31][16 * qc + a_off]));
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
@@ -329,8 +326,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
             int col = 32 * dt + (lane & 31);
             qtmp[i] = q_lds[cur][row][col ^ ((row & 7) << 3)];
           }
-          fb3_bf16x8 bf = __builtin_bit_cast(
-              fb3_bf16x8, *reinterpret_cast<short8*>(qtmp));
+          bf16x8 bf = __builtin_bit_cast(
+              bf16x8, *reinterpret_cast<short8*>(qtmp));
           dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               af, bf, dk_acc[dt], 0, 0, 0);
         }
@@ -357,12 +354,6 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
 // tile), XOR-swizzled row reads, cvt_pk+permlane dS
 // exchange.  dQ[q][d] += sum_k dS^T[k][q] K[k][d]
 // ---------------------------------------------------------------------
-
-DEV_INLINE unsigned int fb3_cvt_pk(float lo, float hi) {
-  unsigned int r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
 
 extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
     const short* __restrict__ Q, const short* __restrict__ K,
@@ -393,23 +384,23 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
            : (((long long)b * Hkv + hkv) * T) * FB3_D;
   const int my_q = q0 + wave * 32 + (lane & 31);
 
-  fb3_bf16x8 q_frag[8], do_frag[8];
+  bf16x8 q_frag[8], do_frag[8];
   {
     const short* qp = Q + qbase + ((long long)wave * 32 + (lane & 31)) * q_rs;
     const short* dp = dO + qbase + ((long long)wave * 32 + (lane & 31)) * q_rs;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      q_frag[c] = fb3_ld8(qp + 16 * c + a_off);
-      do_frag[c] = fb3_ld8(dp + 16 * c + a_off);
+      q_frag[c] = ld8(qp + 16 * c + a_off);
+      do_frag[c] = ld8(dp + 16 * c + a_off);
     }
   }
   const float L2E = 1.4426950408889634f;
   const float lse_q = LSE[((long long)b * Hq + hq) * T + my_q];
   const float d_q = Dsum[((long long)b * Hq + hq) * T + my_q];
 
-  fb3_f32x16 dq_acc[4];
+  f32x16 dq_acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dq_acc[t] = fb3_f32x16{};
+  for (int t = 0; t < 4; ++t) dq_acc[t] = f32x16{};
 
   const int wave_k_max = q0 + wave * 32 + 31;  // last k this wave needs
   const int k_end = causal ? min(T, q0 + 128) : T;
@@ -443,7 +434,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
 
     if (!(causal && k0 > wave_k_max)) {
       // S' = K·Q^T and dP^T = V·dO^T (both [k][q], lane owns column q)
-      fb3_f32x16 s_acc{}, dp_acc{};
+      f32x16 s_acc{}, dp_acc{};
       {
         const int rr = lane & 31;
         const short* krow = &k_lds[cur][rr][0];
@@ -451,8 +442,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
         const int sw = (rr & 7) << 3;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          fb3_bf16x8 kf = fb3_ld8(krow + ((16 * c + a_off) ^ sw));
-          fb3_bf16x8 vf = fb3_ld8(vrow + ((16 * c + a_off) ^ sw));
+          bf16x8 kf = ld8(krow + ((16 * c + a_off) ^ sw));
+          bf16x8 vf = ld8(vrow + ((16 * c + a_off) ^ sw));
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, q_frag[c],
                                                           s_acc, 0, 0, 0);
           dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, do_frag[c],
@@ -474,16 +465,15 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
       // dS A-fragments via cvt_pk+permlane (T12), then dQ += dS·K
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc) {
-        unsigned int a0 = fb3_cvt_pk(ds[8 * kc + 0], ds[8 * kc + 1]);
-        unsigned int a1 = fb3_cvt_pk(ds[8 * kc + 2], ds[8 * kc + 3]);
-        unsigned int b0 = fb3_cvt_pk(ds[8 * kc + 4], ds[8 * kc + 5]);
-        unsigned int b1 = fb3_cvt_pk(ds[8 * kc + 6], ds[8 * kc + 7]);
+        unsigned int a0 = cvt_pk_asm(ds[8 * kc + 0], ds[8 * kc + 1]);
+        unsigned int a1 = cvt_pk_asm(ds[8 * kc + 2], ds[8 * kc + 3]);
+        unsigned int b0 = cvt_pk_asm(ds[8 * kc + 4], ds[8 * kc + 5]);
+        unsigned int b1 = cvt_pk_asm(ds[8 * kc + 6], ds[8 * kc + 7]);
         auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        typedef __attribute__((ext_vector_type(4))) unsigned int fb3_u32x4;
-        fb3_u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
-                     (unsigned)sw1[1]};
-        fb3_bf16x8 af = __builtin_bit_cast(fb3_bf16x8, pw);
+        u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
+                 (unsigned)sw1[1]};
+        bf16x8 af = __builtin_bit_cast(bf16x8, pw);
         {
           const int gl = lane & 15;
           const int grp16 = (lane >> 4) & 1;
@@ -501,8 +491,8 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
 #pragma unroll
               for (int j = 0; j < 4; ++j) ktmp[4 * h + j] = r4[j];
             }
-            fb3_bf16x8 bf = __builtin_bit_cast(
-                fb3_bf16x8, *reinterpret_cast<short8*>(ktmp));
+            bf16x8 bf = __builtin_bit_cast(
+                bf16x8, *reinterpret_cast<short8*>(ktmp));
             dq_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                 af, bf, dq_acc[dt], 0, 0, 0);
           }

@@ -11,15 +11,13 @@
 // WAVES x 32 query rows per block. The binding launches 4 waves
 // (128-row tiles) until those make PP_WIDE_TILE_BLOCKS blocks, then 8
 // (256-row tiles, which stage each K/V tile half as often per query
-// row). The math is flash_attn_v6's swapped-operand form on
-// mfma_f32_32x32x16_bf16 (S' = K.Q^T so a lane owns one query column,
-// lane-local fp32 online softmax in exp2 form with defer-max, P to
-// B-fragments by cvt_pk + permlane32_swap, V^T by ds_read_tr16_b64),
-// with the same fragment layouts and K XOR-swizzle. What differs is the
-// staging: a KV tile is 64 tokens = 4 pages; each 16-row slab of a tile
-// is the contiguous PAGE*D block of one (page, kv head), found through
-// the block table, clamped into the pool, and copied in 8-element
-// chunks into double-buffered LDS while the previous tile computes.
+// row). The math is the swapped-operand tile math of fa_tile.h (s_tile,
+// softmax_step with causal always on, pv_tile) over a K-swizzled LDS
+// tile. This kernel's own part is the staging: a KV tile is 64 tokens =
+// 4 pages; each 16-row slab of a tile is the contiguous PAGE*D block of
+// one (page, kv head), found through the block table, clamped into the
+// pool, and copied in 8-element chunks into double-buffered LDS while the
+// previous tile computes.
 //
 // Cache rows at or beyond ctx + q_len (tail slots of the last page,
 // unused table entries, the null page) are never loaded: they are
@@ -38,7 +36,7 @@
 // `scale` by the binding, v_scale (oscale) into the final 1/l.
 #include <type_traits>
 
-#include "common.h"
+#include "fa_tile.h"
 
 #define PP_PAGE 16
 #define PP_QW 32                      // query rows per wave
@@ -46,36 +44,20 @@
 // 128-row query tiles at or past which the binding picks 256-row tiles
 #define PP_WIDE_TILE_BLOCKS 512
 
-typedef __attribute__((ext_vector_type(8))) __bf16 pp_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float pp_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int pp_u32x4;
-
-DEV_INLINE pp_bf16x8 pp_ld8(const short* p) {
-  short8 s = *reinterpret_cast<const short8*>(p);
-  return __builtin_bit_cast(pp_bf16x8, s);
-}
-
-// v_cvt_pk_bf16_f32: 2 f32 -> packed 2x bf16
-DEV_INLINE unsigned int pp_cvt_pk(float lo, float hi) {
-  unsigned int r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
 typedef __attribute__((ext_vector_type(2))) int pp_int2;
 
 // a staged 8-element chunk as bf16: bf16 chunks as they are
 DEV_INLINE short8 pp_stage_bf16(const short8 x) { return x; }
 
+// fp8 chunks converted; the result goes to LDS, not to an MFMA
 DEV_INLINE short8 pp_stage_bf16(const pp_int2 x) {
-  typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
   u32x4 w;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const float2v lo = __builtin_amdgcn_cvt_pk_f32_fp8(x[i], false);
     const float2v hi = __builtin_amdgcn_cvt_pk_f32_fp8(x[i], true);
-    w[2 * i] = pp_cvt_pk(lo[0], lo[1]);
-    w[2 * i + 1] = pp_cvt_pk(hi[0], hi[1]);
+    w[2 * i] = cvt_pk_asm(lo[0], lo[1]);
+    w[2 * i + 1] = cvt_pk_asm(hi[0], hi[1]);
   }
   return __builtin_bit_cast(short8, w);
 }
@@ -149,19 +131,19 @@ paged_attn_prefill_kernel(
 
   // Q fragments (B operand): a lane reads its own query row; rows past
   // q_len (and so any row past Tq) are zeros and are never dereferenced
-  pp_bf16x8 q_frag[QC];
+  bf16x8 q_frag[QC];
   {
     const bool q_ok = my_q < qlen;
     const short8 zero = short8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < QC; ++c)
-      q_frag[c] = q_ok ? pp_ld8(Q + my_row + 16 * c + a_off)
-                       : __builtin_bit_cast(pp_bf16x8, zero);
+      q_frag[c] = q_ok ? ld8(Q + my_row + 16 * c + a_off)
+                       : __builtin_bit_cast(bf16x8, zero);
   }
 
-  pp_f32x16 o_acc[DT];
+  f32x16 o_acc[DT];
 #pragma unroll
-  for (int t = 0; t < DT; ++t) o_acc[t] = pp_f32x16{};
+  for (int t = 0; t < DT; ++t) o_acc[t] = f32x16{};
   float m_run = -INFINITY, l_run = 0.f;
 
   // KV rows this query tile can see; tiles above the diagonal are skipped
@@ -222,8 +204,7 @@ paged_attn_prefill_kernel(
       const int i = threadIdx.x + PP_THREADS * j;                         \
       const int r = i / CPR;                                              \
       const int c = (i % CPR) * 8;                                        \
-      /* K swizzled: col_shorts ^= (row&7)<<3 */                          \
-      *reinterpret_cast<short8*>(&k_lds[buf][r][c ^ ((r & 7) << 3)]) =    \
+      *reinterpret_cast<short8*>(&k_lds[buf][r][k_swz(r, c)]) =           \
           pp_stage_bf16(k_stage[j]);                                      \
       *reinterpret_cast<short8*>(&v_lds[buf][r][c]) =                     \
           pp_stage_bf16(v_stage[j]);                                      \
@@ -238,9 +219,6 @@ paged_attn_prefill_kernel(
   PP_WRITE_TILE(0);
   __syncthreads();
 
-  const float THR = 8.f;  // defer-max threshold
-  const float L2E = 1.4426950408889634f;
-
   for (int t = 0; t < n_tiles; ++t) {
     const int cur = t & 1;
     const int k0 = t * PP_BN;
@@ -253,112 +231,17 @@ paged_attn_prefill_kernel(
       const bool do0 = (k0 < k_end);
       const bool do1 = (k0 + 32 < k_end) && (k0 + 32 <= wave_gq_max);
 
-      auto s_mfma = [&](int kt) {
-        pp_f32x16 acc{};
-        const int rr = 32 * kt + (lane & 31);
-        const short* krow = &k_lds[cur][rr][0];
-        const int sw = (rr & 7) << 3;
-#pragma unroll
-        for (int c = 0; c < QC; ++c) {
-          pp_bf16x8 kf = pp_ld8(krow + ((16 * c + a_off) ^ sw));
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, q_frag[c], acc,
-                                                        0, 0, 0);
-        }
-        return acc;
+      auto softmax_pv = [&](int kt, f32x16 s_acc) {
+        const f32x16 p =
+            softmax_step<DT>(s_acc, o_acc, m_run, l_run, k0 + 32 * kt, k_end,
+                             true, gq, wave_gq_min, scale, hi);
+        pv_tile(p, v_lds[cur], kt, lane, hi, o_acc);
       };
 
-      auto softmax_pv = [&](int kt, pp_f32x16 s_acc) {
-        const int k0s = k0 + 32 * kt;
-        const bool full_tile =
-            (k0s + 32 <= k_end) && (k0s + 31 <= wave_gq_min);
-        float p_reg[16];
-        float rmax = -INFINITY;
-        if (full_tile) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            p_reg[r] = s_acc[r] * scale;
-            rmax = fmaxf(rmax, p_reg[r]);
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const int gk = k0s + krow;
-            const float sv = s_acc[r] * scale;
-            const bool masked = (gk >= k_end) || (gk > gq);
-            p_reg[r] = masked ? -INFINITY : sv;
-            rmax = fmaxf(rmax, p_reg[r]);
-          }
-        }
-        rmax = fmaxf(rmax, __shfl_xor(rmax, 32, 64));
-        const bool need_rescale =
-            (m_run == -INFINITY) || (rmax - m_run > THR);
-        const float m_new = need_rescale ? fmaxf(m_run, rmax) : m_run;
-        float sc = 1.f;
-        if (need_rescale)
-          sc = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
-        if (m_new == -INFINITY) sc = 0.f;
-        const float mb = m_new * L2E;
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float p = (m_new == -INFINITY)
-                              ? 0.f
-                              : __builtin_amdgcn_exp2f(
-                                    __builtin_fmaf(p_reg[r], L2E, -mb));
-          p_reg[r] = p;
-          psum += p;
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * sc + psum;
-        m_run = m_new;
-
-        if (need_rescale) {
-#pragma unroll
-          for (int d = 0; d < DT; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o_acc[d][r] *= sc;
-        }
-
-        // P -> B-fragments via cvt_pk + permlane32_swap, then PV with
-        // V^T A-fragments from ds_read_tr16_b64 (flash_attn_v6.hip has
-        // the lane maps)
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc) {
-          unsigned int a0 = pp_cvt_pk(p_reg[8 * kc + 0], p_reg[8 * kc + 1]);
-          unsigned int a1 = pp_cvt_pk(p_reg[8 * kc + 2], p_reg[8 * kc + 3]);
-          unsigned int b0 = pp_cvt_pk(p_reg[8 * kc + 4], p_reg[8 * kc + 5]);
-          unsigned int b1 = pp_cvt_pk(p_reg[8 * kc + 6], p_reg[8 * kc + 7]);
-          auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-          auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-          pp_u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
-                      (unsigned)sw1[1]};
-          pp_bf16x8 pb = __builtin_bit_cast(pp_bf16x8, pw);
-          const int gl = lane & 15;
-          const int grp16 = (lane >> 4) & 1;
-          const int vrow0 = 32 * kt + kc * 16 + a_off + (gl >> 2);
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            const int vcol = dt * 32 + 16 * grp16 + 4 * (gl & 3);
-            auto p0 = (__attribute__((address_space(3))) short4v*)
-                &v_lds[cur][vrow0][vcol];
-            auto p1 = (__attribute__((address_space(3))) short4v*)
-                &v_lds[cur][vrow0 + 4][vcol];
-            short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p0);
-            short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p1);
-            short vtmp[8] = {lo[0], lo[1], lo[2], lo[3],
-                             hi4[0], hi4[1], hi4[2], hi4[3]};
-            pp_bf16x8 va = __builtin_bit_cast(
-                pp_bf16x8, *reinterpret_cast<short8*>(vtmp));
-            o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                va, pb, o_acc[dt], 0, 0, 0);
-          }
-        }
-      };
-
-      pp_f32x16 sA{}, sB{};
-      if (do0) sA = s_mfma(0);
-      if (do1) sB = s_mfma(1);  // in flight under sub-tile 0's softmax
+      f32x16 sA{}, sB{};
+      if (do0) sA = s_tile(k_lds[cur], 0, lane, hi, q_frag);
+      // in flight under sub-tile 0's softmax
+      if (do1) sB = s_tile(k_lds[cur], 1, lane, hi, q_frag);
       if (do0) softmax_pv(0, sA);
       if (do1) softmax_pv(1, sB);
     }

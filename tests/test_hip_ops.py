@@ -277,6 +277,44 @@ def test_flash_attention_fwd_full():
 
 
 @GPU
+@pytest.mark.parametrize(
+    "T,Tk,causal",
+    [
+        # 256-row kernel (T % 256 == 0)
+        (256, 320, True),    # diagonal inside the second 64-row tile
+        (256, 300, False),   # ragged key tail: zero-staged rows masked
+        (256, 40, False),    # one partial tile, second sub-tile partly valid
+        (512, 512, True),    # two query tiles, upper key tiles skipped
+        # 128-row kernel
+        (128, 128, True),
+        (384, 384, True),
+        (128, 200, False),
+        (100, 100, True),    # padded to 128 inside flash_attention
+    ],
+)
+def test_flash_attention_fwd_masked_tiles(T, Tk, causal):
+    """The masked-tile path of the shared online-softmax step: key tails,
+    the causal diagonal and its offset. The reference aligns queries to
+    the end of the keys, hence q_offset = Tk - T for the causal cases."""
+    dev = _cuda()
+    torch.manual_seed(2)
+    B, Hq, Hkv, D = 1, 4, 2, 128
+    q = torch.randn(B, Hq, T, D, device=dev, dtype=torch.bfloat16)
+    k = torch.randn(B, Hkv, Tk, D, device=dev, dtype=torch.bfloat16)
+    v = torch.randn(B, Hkv, Tk, D, device=dev, dtype=torch.bfloat16)
+    out, lse = ops.flash_attention(
+        q, k, v, causal=causal, q_offset=Tk - T if causal else 0,
+        return_lse=True)
+    ref, lse_ref = ops.flash_attention_ref(q, k, v, causal=causal)
+    err = (out.float() - ref.float()).abs().max()
+    lse_err = (lse - lse_ref).abs().max()
+    print(f"T {T} Tk {Tk} causal {causal}: max |out - ref| {float(err):.3e}, "
+          f"max |lse - ref| {float(lse_err):.3e}")
+    assert torch.allclose(out.float(), ref.float(), atol=4e-2, rtol=4e-2), err
+    assert torch.allclose(lse, lse_ref, atol=2e-2, rtol=2e-2), lse_err
+
+
+@GPU
 def test_flash_attention_vs_sdpa_speed():
     import time
 
