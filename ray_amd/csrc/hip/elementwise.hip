@@ -61,7 +61,110 @@ extern "C" __global__ __launch_bounds__(256) void swiglu_bwd_bf16(
 // contiguous, larger when x is a no-copy slice of a fused-QKV GEMM
 // output (the [H,D] tail of each row stays contiguous). y is always
 // written contiguous, so RoPE doubles as the gather.
+// The rotation as rope_fwd_scalar_bf16 is compiled (and as every earlier
+// revision computed it): one product rounded, the other fused into the sum.
+// Written out, because left to the compiler's contraction the 16-byte
+// kernels fused the other product of the second line, which moves bits.
+DEV_INLINE float rope_lo(float x1, float x2, float c, float s) {
+  return __builtin_fmaf(x1, c, -(x2 * s));
+}
+DEV_INLINE float rope_hi(float x1, float x2, float c, float s) {
+  return __builtin_fmaf(x1, s, x2 * c);
+}
+
+// One work item is eight pairs of one head vector: two 16-byte loads, two
+// float4 pairs of cos/sin, two 16-byte stores. Needs D % 16 == 0,
+// in_rs % 8 == 0 and 16-byte-aligned x, cosT and sinT; rope_lo / rope_hi
+// give the bits of rope_fwd_scalar_bf16.
 extern "C" __global__ __launch_bounds__(256) void rope_fwd_bf16(
+    const short* __restrict__ x, short* __restrict__ y,
+    const float* __restrict__ cosT, const float* __restrict__ sinT,
+    long long rows, int D, int n_heads, int T, int sign,
+    long long in_rs) {
+  int half = D / 2;
+  int groups = half / 8;
+  long long total = rows * groups;
+  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  long long stride = gridDim.x * (long long)blockDim.x;
+  for (; i < total; i += stride) {
+    long long row = i / groups;
+    int d = (int)(i - row * groups) * 8;
+    long long sr = row / n_heads;           // (b,t) super-row
+    int h = (int)(row - sr * n_heads);
+    int t = (int)(sr % T);
+    const float4v* cp =
+        reinterpret_cast<const float4v*>(cosT + (long long)t * half + d);
+    const float4v* sp =
+        reinterpret_cast<const float4v*>(sinT + (long long)t * half + d);
+    float4v c4[2] = {cp[0], cp[1]};
+    float4v s4[2] = {sp[0], sp[1]};
+    long long src = sr * in_rs + (long long)h * D + d;
+    long long dst = row * D + d;
+    short8 a = *reinterpret_cast<const short8*>(x + src);
+    short8 b = *reinterpret_cast<const short8*>(x + src + half);
+    short8 o1, o2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float c = c4[j >> 2][j & 3];
+      float s = s4[j >> 2][j & 3] * (float)sign;
+      float x1 = bf2f(a[j]);
+      float x2 = bf2f(b[j]);
+      o1[j] = f2bf(rope_lo(x1, x2, c, s));
+      o2[j] = f2bf(rope_hi(x1, x2, c, s));
+    }
+    *reinterpret_cast<short8*>(y + dst) = o1;
+    *reinterpret_cast<short8*>(y + dst + half) = o2;
+  }
+}
+
+// Rotates the q and k sections of a packed QKV buffer in place, one
+// launch: rows of `rs` elements, the first n_rot head vectors of each row
+// (Hq q heads, then Hkv k heads) are rotated, every other column (v, and
+// whatever lies past it) is left alone. sign = -1 is the inverse rotation.
+// A lane reads the eight pairs it writes, so there is no hazard. Needs
+// D % 16 == 0, rs % 8 == 0, 16-byte-aligned buf, cosT and sinT. Same
+// rope_lo / rope_hi per pair as rope_fwd_bf16: the bits are equal.
+extern "C" __global__ __launch_bounds__(256) void rope_qk_inplace_bf16(
+    short* __restrict__ buf, const float* __restrict__ cosT,
+    const float* __restrict__ sinT, long long n_tok, int D, int n_rot, int T,
+    int sign, long long rs) {
+  int half = D / 2;
+  int groups = half / 8;
+  long long total = n_tok * n_rot * groups;
+  long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  long long stride = gridDim.x * (long long)blockDim.x;
+  for (; i < total; i += stride) {
+    long long row = i / groups;
+    int d = (int)(i - row * groups) * 8;
+    long long sr = row / n_rot;             // (b,t) super-row
+    int h = (int)(row - sr * n_rot);
+    int t = (int)(sr % T);
+    const float4v* cp =
+        reinterpret_cast<const float4v*>(cosT + (long long)t * half + d);
+    const float4v* sp =
+        reinterpret_cast<const float4v*>(sinT + (long long)t * half + d);
+    float4v c4[2] = {cp[0], cp[1]};
+    float4v s4[2] = {sp[0], sp[1]};
+    short* p = buf + sr * rs + (long long)h * D + d;
+    short8 a = *reinterpret_cast<const short8*>(p);
+    short8 b = *reinterpret_cast<const short8*>(p + half);
+    short8 o1, o2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float c = c4[j >> 2][j & 3];
+      float s = s4[j >> 2][j & 3] * (float)sign;
+      float x1 = bf2f(a[j]);
+      float x2 = bf2f(b[j]);
+      o1[j] = f2bf(rope_lo(x1, x2, c, s));
+      o2[j] = f2bf(rope_hi(x1, x2, c, s));
+    }
+    *reinterpret_cast<short8*>(p) = o1;
+    *reinterpret_cast<short8*>(p + half) = o2;
+  }
+}
+
+// One pair per work item: any even D and any alignment.
+extern "C" __global__ __launch_bounds__(256) void rope_fwd_scalar_bf16(
     const short* __restrict__ x, short* __restrict__ y,
     const float* __restrict__ cosT, const float* __restrict__ sinT,
     long long rows, int D, int n_heads, int T, int sign,

@@ -43,7 +43,12 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ Dsum,
     short* __restrict__ dK, short* __restrict__ dV, int B, int Hq,
-    int Hkv, int T, int causal, float scale, int bthd) {
+    int Hkv, int T, int causal, float scale, int bthd, int q_rs_, int o_rs_,
+    int kv_rs_, int dkv_rs_) {
+  // bthd=1: token-row storage with row strides (elements) q_rs for Q, o_rs
+  // for dO, kv_rs for K/V and dkv_rs for dK/dV (a [B,T,H,D] tensor or a
+  // column section of a packed [B,T,rs] buffer); bthd=0: contiguous
+  // [B,H,T,D], every stride is D.
   __shared__ __attribute__((aligned(16))) short smem[65536 + 512];
   // q and dO first: every tile read is then base + immediate (< 64 KB)
   short* const q_lds = smem;                  // [2][64][128]
@@ -63,11 +68,12 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
   const int lane = tid & 63;
   const int hi = lane >> 5;
 
-  const long long q_rs = bthd ? (long long)Hq * FB3_D : FB3_D;
-  const long long kv_rs = bthd ? (long long)Hkv * FB3_D : FB3_D;
+  const long long q_rs = q_rs_, o_rs = o_rs_, kv_rs = kv_rs_, dkv_rs = dkv_rs_;
   const long long kbase =
-      bthd ? (((long long)b * T + k0) * Hkv + hkv) * FB3_D
+      bthd ? ((long long)b * T + k0) * kv_rs + hkv * FB3_D
            : (((long long)b * Hkv + hkv) * T + k0) * FB3_D;
+  const long long dkbase =
+      bthd ? ((long long)b * T + k0) * dkv_rs + hkv * FB3_D : kbase;
 
   // K register-resident (B operand of S: lane = key, 8 d per k-step half);
   // V into LDS once.
@@ -107,27 +113,29 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
   const int st_r = tid >> 4;  // + 32 * j
   const int st_c = tid & 15;
   // lane part of a staged chunk's global offset (a tile is < 2^31 elements
-  // from its first row: 64 rows x Hq x 128); the tile part is scalar
+  // from its first row: the host checks 64 rows x row stride); the tile
+  // part is scalar. Q and dO have a row stride each.
   const unsigned st_go = (unsigned)(st_r * (int)q_rs + 8 * st_c);
+  const unsigned st_go_do = (unsigned)(st_r * (int)o_rs + 8 * st_c);
   // wave 0 stages -LSE/scale, wave 1 stages -delta (lse_lds, dsum_lds are
   // adjacent)
   const float* const c_src = wave == 0 ? LSE : Dsum;
   const float c_div = wave == 0 ? scale : 1.f;
   float* const c_dst = lse_lds + 2 * FB3_QT * wave;
 
-#define FB6_TILE_BASE(t_idx)                                              \
+#define FB6_TILE_BASE(t_idx, rs_)                                         \
   const int g_ = (t_idx) / nq;                                            \
   const int q0_ = q_start + ((t_idx) - g_ * nq) * FB3_QT;                 \
   const int hq_ = hkv * rep + g_;                                         \
   const long long qb_ =                                                   \
-      (bthd ? ((long long)b * T * Hq + hq_) * FB3_D                       \
+      (bthd ? (long long)b * T * (rs_) + hq_ * FB3_D                      \
             : (((long long)b * Hq + hq_) * T) * FB3_D) +                  \
-      (long long)q0_ * q_rs;                                              \
+      (long long)q0_ * (rs_);                                             \
   const long long lb_ = ((long long)b * Hq + hq_) * T + q0_;
 
 #define FB6_LOAD_Q(t_idx)                                                 \
   do {                                                                    \
-    FB6_TILE_BASE(t_idx)                                                  \
+    FB6_TILE_BASE(t_idx, q_rs)                                            \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                         \
       q_st[j] = *reinterpret_cast<const short8*>(                         \
           Q + qb_ + 32 * j * q_rs + st_go);                               \
@@ -136,11 +144,11 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
 
 #define FB6_LOAD_DO(t_idx)                                                \
   do {                                                                    \
-    FB6_TILE_BASE(t_idx)                                                  \
+    FB6_TILE_BASE(t_idx, o_rs)                                            \
     (void)lb_;                                                            \
     _Pragma("unroll") for (int j = 0; j < 2; ++j)                         \
       do_st[j] = *reinterpret_cast<const short8*>(                        \
-          dO + qb_ + 32 * j * q_rs + st_go);                              \
+          dO + qb_ + 32 * j * o_rs + st_go_do);                           \
   } while (0)
 
 #define FB6_WRITE_Q(buf)                                                  \
@@ -304,7 +312,8 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
   short* const ep = smem + wave * (32 * FB6_EP_STRIDE);
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
-    short* out = (pass == 0 ? dK : dV) + kbase + (long long)wave * 32 * kv_rs;
+    short* out =
+        (pass == 0 ? dK : dV) + dkbase + (long long)wave * 32 * dkv_rs;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -320,7 +329,7 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
       const int i = el + 64 * j;
       const int row = i >> 4;
       const int ch = i & 15;
-      *reinterpret_cast<short8*>(out + (long long)row * kv_rs + 8 * ch) =
+      *reinterpret_cast<short8*>(out + (long long)row * dkv_rs + 8 * ch) =
           *reinterpret_cast<const short8*>(ep + row * FB6_EP_STRIDE + 8 * ch);
     }
   }

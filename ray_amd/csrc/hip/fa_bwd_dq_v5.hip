@@ -22,11 +22,18 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ Dsum,
     short* __restrict__ dQ, int B, int Hq, int Hkv, int T, int causal,
-    float scale, int bthd) {
+    float scale, int bthd, int q_rs_, int o_rs_, int kv_rs_, int dq_rs_) {
+  // bthd=1: token-row storage with row strides (elements) q_rs for Q, o_rs
+  // for dO, kv_rs for K/V and dq_rs for dQ (a [B,T,H,D] tensor or a column
+  // section of a packed [B,T,rs] buffer); bthd=0: contiguous [B,H,T,D],
+  // every stride is D. 32-bit arguments: a row offset is then one
+  // 32 x 32 -> 64-bit multiply-add.
   __shared__ __attribute__((aligned(16))) short k_lds[2 * FB5_KT * FB3_D];
   __shared__ __attribute__((aligned(16))) short v_lds[2 * FB5_KT * FB3_D];
 
-  const int q0 = blockIdx.x * 256;
+  // heaviest causal block (the last query rows) first: the light blocks
+  // fill the tail of the grid
+  const int q0 = (gridDim.x - 1 - blockIdx.x) * 256;
   const int bh = blockIdx.y;
   const int b = bh / Hq;
   const int hq = bh % Hq;
@@ -36,20 +43,23 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
   const int lane = tid & 63;
   const int hi = lane >> 5;
 
-  const long long q_rs = bthd ? (long long)Hq * FB3_D : FB3_D;
-  const long long kv_rs = bthd ? (long long)Hkv * FB3_D : FB3_D;
+  const long long q_rs = q_rs_, o_rs = o_rs_, kv_rs = kv_rs_, dq_rs = dq_rs_;
   const long long qbase =
-      bthd ? (((long long)b * T + q0) * Hq + hq) * FB3_D
+      bthd ? ((long long)b * T + q0) * q_rs + hq * FB3_D
            : (((long long)b * Hq + hq) * T + q0) * FB3_D;
+  const long long obase =
+      bthd ? ((long long)b * T + q0) * o_rs + hq * FB3_D : qbase;
+  const long long dqbase =
+      bthd ? ((long long)b * T + q0) * dq_rs + hq * FB3_D : qbase;
   const long long kbase =
-      bthd ? ((long long)b * T * Hkv + hkv) * FB3_D
+      bthd ? (long long)b * T * kv_rs + hkv * FB3_D
            : (((long long)b * Hkv + hkv) * T) * FB3_D;
   const int my_q = q0 + wave * 32 + (lane & 31);
 
   bf16x8 q_frag[8], do_frag[8];
   {
     const short* qp = Q + qbase + ((long long)wave * 32 + (lane & 31)) * q_rs;
-    const short* dp = dO + qbase + ((long long)wave * 32 + (lane & 31)) * q_rs;
+    const short* dp = dO + obase + ((long long)wave * 32 + (lane & 31)) * o_rs;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       q_frag[c] = ld8(qp + 16 * c + 8 * hi);
@@ -198,13 +208,13 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
 #undef FB5_DQ_LOAD
 #undef FB5_DQ_WRITE
 
-  short* out = dQ + qbase + (long long)wave * 32 * q_rs;
+  short* out = dQ + dqbase + (long long)wave * 32 * dq_rs;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int qrow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      out[(long long)qrow * q_rs + 32 * dt + (lane & 31)] =
+      out[(long long)qrow * dq_rs + 32 * dt + (lane & 31)] =
           f2bf(dq_acc[dt][r]);
     }
 }

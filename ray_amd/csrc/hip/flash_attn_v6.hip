@@ -26,13 +26,20 @@ flash_attn_fwd_v6_bf16(const short* __restrict__ Q,
                        const short* __restrict__ V, short* __restrict__ O,
                        float* __restrict__ LSE, int B, int Hq, int Hkv,
                        int T, int Tk, int causal, int q_offset,
-                       float scale, int bthd) {
-  // bthd=1: Q/K/V/O are [B,T,H,D] storage (the model's natural layout
-  // after RoPE — no transpose-contiguous copies); bthd=0: [B,H,T,D].
+                       float scale, int bthd, int q_rs_, int o_rs_,
+                       int kv_rs_) {
+  // bthd=1: Q/K/V/O are token-row storage (the model's natural layout:
+  // [B,T,H,D], or the q/k/v column sections of one packed [B,T,rs] GEMM
+  // output); q_rs, o_rs and kv_rs are the token-row strides in elements
+  // of Q, of O and of K/V, each >= H*D. bthd=0: contiguous [B,H,T,D],
+  // all three strides are D. They are 32-bit arguments: a row offset is
+  // then one 32 x 32 -> 64-bit multiply-add.
   __shared__ short k_lds[2][FA6_BN][FA6_D];
   __shared__ short v_lds[2][FA6_BN][FA6_D];
 
-  const int q0 = blockIdx.x * FA6_BM;
+  // heaviest causal block (the last query rows) first: the light blocks
+  // fill the tail of the grid
+  const int q0 = (gridDim.x - 1 - blockIdx.x) * FA6_BM;
   const int bh = blockIdx.y;
   const int b = bh / Hq;
   const int hq = bh % Hq;
@@ -43,13 +50,14 @@ flash_attn_fwd_v6_bf16(const short* __restrict__ Q,
   const int hi = lane >> 5;
   const int a_off = 8 * hi;
 
-  const long long q_rs = bthd ? (long long)Hq * FA6_D : FA6_D;
-  const long long kv_rs = bthd ? (long long)Hkv * FA6_D : FA6_D;
+  const long long q_rs = q_rs_, o_rs = o_rs_, kv_rs = kv_rs_;
   const long long qbase =
-      bthd ? (((long long)b * T + q0) * Hq + hq) * FA6_D
+      bthd ? ((long long)b * T + q0) * q_rs + hq * FA6_D
            : (((long long)b * Hq + hq) * T + q0) * FA6_D;
+  const long long obase =
+      bthd ? ((long long)b * T + q0) * o_rs + hq * FA6_D : qbase;
   const long long kbase =
-      bthd ? ((long long)b * Tk * Hkv + hkv) * FA6_D
+      bthd ? (long long)b * Tk * kv_rs + hkv * FA6_D
            : (((long long)b * Hkv + hkv) * Tk) * FA6_D;
   const int my_q = q0 + wave * FA6_QW + qcol;
   const int gq = q_offset + my_q;                  // causal-global index
@@ -154,7 +162,7 @@ flash_attn_fwd_v6_bf16(const short* __restrict__ Q,
   // ---- epilogue: O[q][d] = O'[d][q] / l ----
   float inv = (l_run > 0.f) ? 1.f / l_run : 0.f;
   if (my_q < T) {
-    short* op = O + qbase + ((long long)wave * FA6_QW + qcol) * q_rs;
+    short* op = O + obase + ((long long)wave * FA6_QW + qcol) * o_rs;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll

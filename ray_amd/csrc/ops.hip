@@ -71,16 +71,31 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
   return {y, inv};
 }
 
-std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
-                                    at::Tensor inv) {
+static long long rmsnorm_bwd_check(const at::Tensor& dy, const at::Tensor& x,
+                                   const at::Tensor& w, const at::Tensor& inv,
+                                   int* H_out) {
   CHECK_RMS_BF16(dy); CHECK_RMS_BF16(x); CHECK_RMS_BF16(w); CHECK_IN(inv);
   int H = rmsnorm_check_hw(x, w);
   long long N = x.numel() / H;
   TORCH_CHECK(dy.sizes() == x.sizes(), "rmsnorm: dy must have x's shape");
   TORCH_CHECK(inv.scalar_type() == at::kFloat && inv.numel() == N,
               "rmsnorm: inv must be fp32 [N]");
+  *H_out = H;
+  return N;
+}
+
+// dx kernel, then a second pass over dy and x for dw (atomic adds across
+// row splits). Serves an H the one-pass kernel's template does not cover
+// (H > 8192). Bound for the tests and tools/glue_bench.py only, which
+// compare the one-pass kernel with it; nothing in the package calls the
+// binding.
+std::vector<at::Tensor> rmsnorm_bwd_two_pass(at::Tensor dy, at::Tensor x,
+                                             at::Tensor w, at::Tensor inv) {
+  int H;
+  long long N = rmsnorm_bwd_check(dy, x, w, inv, &H);
   auto dx = at::empty_like(x);
   auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
+  if (N == 0) return {dx, dw};
   hipLaunchKernelGGL(rmsnorm_bwd_dx_bf16, dim3((unsigned)N), dim3(256), 0,
                      cur_stream(), (const short*)dy.data_ptr(),
                      (const short*)x.data_ptr(), (const short*)w.data_ptr(),
@@ -92,6 +107,107 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                      (const short*)x.data_ptr(), inv.data_ptr<float>(),
                      dw.data_ptr<float>(), N, H);
   return {dx, dw};
+}
+
+static void launch_add_bf16(const at::Tensor& a, const at::Tensor& b,
+                            at::Tensor& y) {
+  long long n8 = a.numel() / 8;
+  if (n8 == 0) return;
+  hipLaunchKernelGGL(add_bf16, dim3(grid_for(n8)), dim3(256), 0, cur_stream(),
+                     (const short*)a.data_ptr(), (const short*)b.data_ptr(),
+                     (short*)y.data_ptr(), n8);
+}
+
+// One pass over dy and x: dx (plus g_res when given, rounded as the bf16
+// add of the two tensors would be) and dw fp32 [H], summed in a fixed order.
+// `grid` overrides the number of blocks (0: the default below); it is there
+// for tools/glue_bench.py and the tests, the package always passes 0.
+std::vector<at::Tensor> rmsnorm_bwd_res(at::Tensor dy, at::Tensor x,
+                                        at::Tensor w, at::Tensor inv,
+                                        c10::optional<at::Tensor> g_res,
+                                        int64_t grid) {
+  int H;
+  long long N = rmsnorm_bwd_check(dy, x, w, inv, &H);
+  const bool res = g_res.has_value();
+  if (res) {
+    CHECK_RMS_BF16((*g_res));
+    TORCH_CHECK(g_res->sizes() == x.sizes(),
+                "rmsnorm: g_res must have x's shape");
+  }
+  TORCH_CHECK(grid >= 0 && grid <= 65536, "rmsnorm: grid must be 0..65536");
+  if (H > 4 * RMS_CHUNK || N == 0) {
+    auto r = rmsnorm_bwd_two_pass(dy, x, w, inv);
+    if (res) {
+      auto sum = at::empty_like(r[0]);
+      launch_add_bf16(r[0], *g_res, sum);
+      r[0] = sum;
+    }
+    return r;
+  }
+  const long long blocks =
+      grid ? grid
+           : std::min<long long>(RMS_BWD_GRID, (N + RMS_BWD_MIN_ROWS - 1) /
+                                                   RMS_BWD_MIN_ROWS);
+  const int G = (int)std::min<long long>(N, blocks);
+  auto dx = at::empty_like(x);
+  auto part = at::empty({G, H}, x.options().dtype(at::kFloat));
+  auto dw = at::empty({H}, x.options().dtype(at::kFloat));
+  const short* gp = res ? (const short*)g_res->data_ptr() : nullptr;
+#define RMS_BWD_LAUNCH(CC, RR)                                              \
+  hipLaunchKernelGGL((rmsnorm_bwd_onepass_bf16<CC, RR>), dim3(G), dim3(256), \
+                     0, cur_stream(), (const short*)dy.data_ptr(),          \
+                     (const short*)x.data_ptr(), (const short*)w.data_ptr(), \
+                     inv.data_ptr<float>(), gp, (short*)dx.data_ptr(),      \
+                     part.data_ptr<float>(), N, H)
+#define RMS_BWD_CHUNKS(CC)                                                  \
+  if (res) { RMS_BWD_LAUNCH(CC, true); } else { RMS_BWD_LAUNCH(CC, false); }
+  if (H <= RMS_CHUNK) { RMS_BWD_CHUNKS(1) }
+  else if (H <= 2 * RMS_CHUNK) { RMS_BWD_CHUNKS(2) }
+  else { RMS_BWD_CHUNKS(4) }
+#undef RMS_BWD_CHUNKS
+#undef RMS_BWD_LAUNCH
+  hipLaunchKernelGGL(rmsnorm_dw_reduce_f32, dim3((H + 31) / 32), dim3(256), 0,
+                     cur_stream(), part.data_ptr<float>(),
+                     dw.data_ptr<float>(), G, H);
+  return {dx, dw};
+}
+
+std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
+                                    at::Tensor inv) {
+  return rmsnorm_bwd_res(dy, x, w, inv, c10::nullopt, 0);
+}
+
+// s = bf16(x + r), h = rmsnorm(s), inv_rms: one pass
+std::vector<at::Tensor> add_rmsnorm_fwd(at::Tensor x, at::Tensor r,
+                                        at::Tensor w, double eps) {
+  CHECK_RMS_BF16(x);
+  CHECK_RMS_BF16(r);
+  CHECK_RMS_BF16(w);
+  int H = rmsnorm_check_hw(x, w);
+  TORCH_CHECK(r.sizes() == x.sizes(), "add_rmsnorm: r must have x's shape");
+  long long N = x.numel() / H;
+  auto s = at::empty_like(x);
+  if (N == 0)
+    return {s, at::empty_like(x),
+            at::empty({0}, x.options().dtype(at::kFloat))};
+  if (H > 4 * RMS_CHUNK) {
+    launch_add_bf16(x, r, s);
+    auto yi = rmsnorm_fwd(s, w, eps);
+    return {s, yi[0], yi[1]};
+  }
+  auto y = at::empty_like(x);
+  auto inv = at::empty({N}, x.options().dtype(at::kFloat));
+#define ADD_RMS_LAUNCH(CC)                                                  \
+  hipLaunchKernelGGL((add_rmsnorm_fwd_bf16<CC>), dim3((unsigned)N),         \
+                     dim3(256), 0, cur_stream(), (const short*)x.data_ptr(), \
+                     (const short*)r.data_ptr(), (const short*)w.data_ptr(), \
+                     (short*)s.data_ptr(), (short*)y.data_ptr(),            \
+                     inv.data_ptr<float>(), H, (float)eps)
+  if (H <= RMS_CHUNK) { ADD_RMS_LAUNCH(1); }
+  else if (H <= 2 * RMS_CHUNK) { ADD_RMS_LAUNCH(2); }
+  else { ADD_RMS_LAUNCH(4); }
+#undef ADD_RMS_LAUNCH
+  return {s, y, inv};
 }
 
 // ---------------- SwiGLU ----------------
@@ -140,12 +256,23 @@ at::Tensor rope_apply(at::Tensor x, at::Tensor cosT, at::Tensor sinT,
                ? at::empty_like(x)
                : at::empty({x.size(0), x.size(1), x.size(2), x.size(3)},
                            x.options());
-  long long total = rows * (D / 2);
-  hipLaunchKernelGGL(rope_fwd_bf16, dim3(grid_for(total)), dim3(256), 0,
-                     cur_stream(), (const short*)x.data_ptr(),
-                     (short*)y.data_ptr(), cosT.data_ptr<float>(),
-                     sinT.data_ptr<float>(), rows, D, (int)n_heads, (int)T,
-                     (int)sign, in_rs);
+  auto aligned16 = [](const at::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  // eight pairs per lane with 16-byte accesses where the layout allows it
+  const bool vec = D % 16 == 0 && in_rs % 8 == 0 && aligned16(x) &&
+                   aligned16(y) && aligned16(cosT) && aligned16(sinT);
+  long long total = vec ? rows * (D / 16) : rows * (D / 2);
+  if (total == 0) return y;
+#define ROPE_LAUNCH(KERNEL)                                                 \
+  hipLaunchKernelGGL(KERNEL, dim3(grid_for(total)), dim3(256), 0,           \
+                     cur_stream(), (const short*)x.data_ptr(),              \
+                     (short*)y.data_ptr(), cosT.data_ptr<float>(),          \
+                     sinT.data_ptr<float>(), rows, D, (int)n_heads, (int)T, \
+                     (int)sign, in_rs)
+  if (vec) { ROPE_LAUNCH(rope_fwd_bf16); }
+  else { ROPE_LAUNCH(rope_fwd_scalar_bf16); }
+#undef ROPE_LAUNCH
   return y;
 }
 
@@ -693,14 +820,25 @@ at::Tensor ce_bwd(at::Tensor logits, at::Tensor target, at::Tensor mx,
 }
 
 
-// Layout of a [B,H,T,D] tensor: 0 = contiguous BHTD, 1 = a transpose
-// view of [B,T,H,D] storage (the model's natural layout), -1 = other.
-static inline int attn_layout(const at::Tensor& t) {
+// Layout of a [B,H,T,D] tensor: 0 = contiguous BHTD; 1 = a transpose view
+// of token-row storage, strides (T*rs, D, rs, 1): [B,T,H,D] storage (the
+// model's natural layout, rs = H*D) or a column section of a wider row,
+// such as the q, k or v part of one packed [B,T,(Hq+2Hkv)*D] GEMM output
+// (rs > H*D, then rs % 8 == 0, a 16-byte-aligned start and offsets that fit
+// the kernels' 32-bit staging arithmetic are required); -1 = other.
+// *rs is the token-row stride in elements (D for layout 0).
+static inline int attn_layout(const at::Tensor& t, long long* rs) {
   if (t.stride(3) != 1) return -1;
-  long long B = t.size(0), H = t.size(1), T = t.size(2), D = t.size(3);
+  long long H = t.size(1), T = t.size(2), D = t.size(3);
+  *rs = D;
   if (t.stride(2) == D && t.stride(1) == T * D && t.stride(0) == H * T * D)
     return 0;
-  if (t.stride(1) == D && t.stride(2) == H * D && t.stride(0) == H * T * D)
+  const long long r = t.stride(2);
+  if (t.stride(1) != D || t.stride(0) != T * r || r < H * D) return -1;
+  *rs = r;
+  if (r == H * D) return 1;
+  if (r % 8 == 0 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+      T * r < (1ll << 31) && 64 * r < (1ll << 30))
     return 1;
   return -1;
 }
@@ -710,8 +848,10 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
                                         int64_t q_offset, bool want_lse) {
   TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(),
               "flash_attn tensors must be on GPU");
-  int bthd = attn_layout(q);
-  TORCH_CHECK(bthd >= 0 && attn_layout(k) == bthd && attn_layout(v) == bthd,
+  long long q_rs, k_rs, v_rs;
+  int bthd = attn_layout(q, &q_rs);
+  TORCH_CHECK(bthd >= 0 && attn_layout(k, &k_rs) == bthd &&
+                  attn_layout(v, &v_rs) == bthd && k_rs == v_rs,
               "q/k/v must share a BHTD-contiguous or BTHD-view layout");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
   TORCH_CHECK(q.size(3) == 128, "head_dim must be 128");
@@ -728,6 +868,7 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
                ? at::empty({B, T, Hq, (int)q.size(3)}, q.options())
                      .permute({0, 2, 1, 3})
                : at::empty_like(q);
+  const long long o_rs = bthd ? (long long)Hq * q.size(3) : q.size(3);
   at::Tensor lse;
   float* lse_ptr = nullptr;
   if (want_lse) {
@@ -744,7 +885,8 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
     // 256 query rows per block: 8-wave dbuf/async-stage/swizzled structure
     hipLaunchKernelGGL(flash_attn_fwd_v6_bf16, dim3(T / 256, B * Hq),
                        dim3(512), 0, cur_stream(), qp, kp, vp, op, lse_ptr,
-                       B, Hq, Hkv, T, Tk, c, qo, scale, bthd);
+                       B, Hq, Hkv, T, Tk, c, qo, scale, bthd, (int)q_rs,
+                       (int)o_rs, (int)k_rs);
   else
     hipLaunchKernelGGL(flash_attn_fwd_v5_bf16, dim3(T / 128, B * Hq),
                        dim3(256), 0, cur_stream(), qp, kp, vp, op, lse_ptr,
@@ -753,14 +895,22 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
   return {o};
 }
 
+// `dqkv`, when given, is a packed gradient buffer [B, T, (Hq+2Hkv)*D] (unit
+// column stride, 16-byte-aligned rows): dq, dk and dv are written into its
+// three column sections and returned as views of it. It needs the BTHD-view
+// layout (only the 256-row kernels write through a row stride).
 std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                                         at::Tensor v, at::Tensor o,
                                         at::Tensor d_o, at::Tensor lse,
-                                        bool causal) {
+                                        bool causal,
+                                        c10::optional<at::Tensor> dqkv) {
   TORCH_CHECK(q.is_cuda(), "flash_attn_bwd tensors must be on GPU");
-  int bthd = attn_layout(q);
-  TORCH_CHECK(bthd >= 0 && attn_layout(k) == bthd && attn_layout(v) == bthd
-                  && attn_layout(o) == bthd && attn_layout(d_o) == bthd,
+  long long q_rs, k_rs, v_rs, o_rs, do_rs;
+  int bthd = attn_layout(q, &q_rs);
+  TORCH_CHECK(bthd >= 0 && attn_layout(k, &k_rs) == bthd &&
+                  attn_layout(v, &v_rs) == bthd &&
+                  attn_layout(o, &o_rs) == bthd &&
+                  attn_layout(d_o, &do_rs) == bthd && k_rs == v_rs,
               "q/k/v/o/dO must share a BHTD or BTHD-view layout");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
   TORCH_CHECK(q.size(3) == 128, "head_dim must be 128");
@@ -774,13 +924,49 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
               "BTHD-view layout needs T % 256 == 0: only the 256-row "
               "kernels read it");
   int D = (int)q.size(3);
-  auto mk_like = [&](const at::Tensor& t, int H) {
-    return bthd ? at::empty({B, T, H, D}, t.options()).permute({0, 2, 1, 3})
-                : at::empty_like(t);
-  };
-  auto dq = mk_like(q, Hq);
-  auto dk = mk_like(k, Hkv);
-  auto dv = mk_like(v, Hkv);
+  // fa_bwd_prep reads o and dO as plain [B,T,Hq,D] rows
+  TORCH_CHECK(!bthd || (o_rs == (long long)Hq * D && do_rs == o_rs),
+              "o and dO must be [B,T,Hq,D] storage in the BTHD-view layout");
+  at::Tensor dq, dk, dv;
+  long long dq_rs = q_rs, dkv_rs = k_rs;
+  if (dqkv.has_value()) {
+    const at::Tensor& g = *dqkv;
+    const long long W = (long long)(Hq + 2 * Hkv) * D;
+    TORCH_CHECK(bthd == 1, "dqkv needs q/k/v in the BTHD-view layout");
+    TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kBFloat16 &&
+                    g.dim() == 3 && g.size(0) == B && g.size(1) == T &&
+                    g.size(2) == W,
+                "dqkv must be bf16 [B, T, (Hq+2Hkv)*D] on the GPU");
+    const long long r = g.stride(1);
+    TORCH_CHECK(g.stride(2) == 1 && g.stride(0) == T * r && r >= W &&
+                    r % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0 &&
+                    T * r < (1ll << 31) && 64 * r < (1ll << 30),
+                "dqkv rows must be 16-byte aligned, at stride >= "
+                "(Hq+2Hkv)*D with T * stride < 2^31");
+    auto section = [&](long long col, int H) {
+      return g.narrow(2, col, (long long)H * D)
+          .view({B, T, H, D})
+          .permute({0, 2, 1, 3});
+    };
+    dq = section(0, Hq);
+    dk = section((long long)Hq * D, Hkv);
+    dv = section((long long)(Hq + Hkv) * D, Hkv);
+    dq_rs = dkv_rs = r;
+  } else {
+    auto mk_like = [&](const at::Tensor& t, int H) {
+      return bthd
+                 ? at::empty({B, T, H, D}, t.options()).permute({0, 2, 1, 3})
+                 : at::empty_like(t);
+    };
+    dq = mk_like(q, Hq);
+    dk = mk_like(k, Hkv);
+    dv = mk_like(v, Hkv);
+    if (bthd) {
+      dq_rs = (long long)Hq * D;
+      dkv_rs = (long long)Hkv * D;
+    }
+  }
   auto dsum = at::empty({B, Hq, T}, q.options().dtype(at::kFloat));
   float scale = 1.0f / sqrtf((float)q.size(3));
   long long rows = (long long)B * Hq * T;
@@ -805,10 +991,12 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
     // block as the slow dimension (heaviest causal block first).
     hipLaunchKernelGGL(fa_bwd_dq_v5_bf16, dim3(T / 256, B * Hq), dim3(512),
                        0, st, qp, kp, vp, dop, lsep, dsp, dqp, B, Hq, Hkv, T,
-                       c, scale, bthd);
+                       c, scale, bthd, (int)q_rs, (int)o_rs, (int)k_rs,
+                       (int)dq_rs);
     hipLaunchKernelGGL(fa_bwd_dkv_v6_bf16, dim3(B * Hkv, T / 256), dim3(512),
                        0, st, qp, kp, vp, dop, lsep, dsp, dkp, dvp, B, Hq,
-                       Hkv, T, c, scale, bthd);
+                       Hkv, T, c, scale, bthd, (int)q_rs, (int)o_rs, (int)k_rs,
+                       (int)dkv_rs);
   } else {
     // 128-row blocks, contiguous BHTD only (checked above): K/V
     // register-resident, 64-row double-buffered q/dO tiles; dV and dK are
@@ -826,9 +1014,51 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
   return {dq, dk, dv};
 }
 
+// In-place RoPE of the q and k sections of a packed [B, T, rs-strided] QKV
+// buffer whose rows begin with Hq q heads, then Hkv k heads, then v.
+void rope_qk_inplace(at::Tensor qkv, at::Tensor cosT, at::Tensor sinT,
+                     int64_t n_heads, int64_t n_kv_heads, int64_t sign) {
+  CHECK_IN(cosT); CHECK_IN(sinT);
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 &&
+                  qkv.dim() == 3,
+              "rope_qk_inplace: qkv must be a bf16 [B, T, W] GPU tensor");
+  TORCH_CHECK(sign == 1 || sign == -1, "rope_qk_inplace: sign must be +-1");
+  TORCH_CHECK(n_heads >= 1 && n_kv_heads >= 1 &&
+                  qkv.size(2) % (n_heads + 2 * n_kv_heads) == 0,
+              "rope_qk_inplace: W must be (Hq + 2 Hkv) * D");
+  const long long B = qkv.size(0), T = qkv.size(1), W = qkv.size(2);
+  const int D = (int)(W / (n_heads + 2 * n_kv_heads));
+  const long long rs = qkv.stride(1);
+  TORCH_CHECK(D > 0 && D % 16 == 0, "rope_qk_inplace: D must be a multiple "
+                                    "of 16");
+  TORCH_CHECK(qkv.stride(2) == 1 && rs >= W && rs % 8 == 0 &&
+                  (B == 1 || qkv.stride(0) == T * rs) &&
+                  reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "rope_qk_inplace: rows must be 16-byte aligned with a uniform "
+              "stride >= W");
+  TORCH_CHECK(cosT.scalar_type() == at::kFloat &&
+                  sinT.scalar_type() == at::kFloat && cosT.dim() == 2 &&
+                  cosT.size(0) >= T && cosT.size(1) == D / 2 &&
+                  sinT.sizes() == cosT.sizes() &&
+                  reinterpret_cast<uintptr_t>(cosT.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(sinT.data_ptr()) % 16 == 0,
+              "rope_qk_inplace: cosT/sinT must be 16-byte-aligned fp32 "
+              "[>= T, D/2]");
+  const int n_rot = (int)(n_heads + n_kv_heads);
+  const long long total = B * T * n_rot * (D / 16);
+  if (total == 0) return;
+  hipLaunchKernelGGL(rope_qk_inplace_bf16, dim3(grid_for(total)), dim3(256), 0,
+                     cur_stream(), (short*)qkv.data_ptr(),
+                     cosT.data_ptr<float>(), sinT.data_ptr<float>(), B * T, D,
+                     n_rot, (int)T, (int)sign, rs);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_fwd", &flash_attn_fwd);
-  m.def("flash_attn_bwd", &flash_attn_bwd);
+  m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("o"), py::arg("d_o"), py::arg("lse"),
+        py::arg("causal"), py::arg("dqkv") = py::none());
+  m.def("rope_qk_inplace", &rope_qk_inplace);
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("gemv", &gemv);
   m.def("gemm_wgrad", &gemm_wgrad, py::arg("dy"), py::arg("x"),
@@ -850,6 +1080,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ctx_lens"), py::arg("q_lens"), py::arg("k_scale") = 1.0,
         py::arg("v_scale") = 1.0);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
+  m.def("rmsnorm_bwd_two_pass", &rmsnorm_bwd_two_pass);
+  m.def("rmsnorm_bwd_res", &rmsnorm_bwd_res, py::arg("dy"), py::arg("x"),
+        py::arg("w"), py::arg("inv"), py::arg("g_res") = py::none(),
+        py::arg("grid") = 0);
+  m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope_apply", &rope_apply);
@@ -860,4 +1095,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
   m.attr("gfx_arch") = "gfx950";
+  // the largest grid of the one-pass RMSNorm backward (tests size N by it)
+  m.attr("rmsnorm_bwd_grid") = RMS_BWD_GRID;
 }

@@ -105,6 +105,25 @@ class Attention(nn.Module):
     def forward(self, x, cosT, sinT, kv_cache=None, pos0: int = 0):
         B, T, H = x.shape
         cfg = self.cfg
+        def flash(t):
+            return (
+                kv_cache is None
+                and t.is_cuda
+                and t.dtype == torch.bfloat16
+                and self.head_dim == 128
+                and T % 128 == 0
+                and not os.environ.get("RAY_AMD_ATTN_SDPA")
+            )
+
+        if (flash(x) and self._fused_qkv and T % 256 == 0 and pos0 == 0
+                and ops._FUSED_QKV_ATTN
+                and self.qkv_proj.weight.dtype == torch.bfloat16):
+            # RoPE in place on the projection output, attention on its
+            # q/k/v column sections, one packed gradient in backward
+            out = ops.qkv_rope_attention(
+                self.qkv_proj(x), cosT, sinT, cfg.num_heads,
+                cfg.num_kv_heads)
+            return self.o_proj(out)
         q, k, v = self.qkv(x)
         if self._fused_qkv:
             v = v.contiguous()  # k/q gather happens inside rope
@@ -120,14 +139,7 @@ class Attention(nn.Module):
         # kernels (fwd v6 + fa_bwd v4: measured at parity with AOTriton
         # round-trip, profiles/flash_attn_v6_bench.log); decode/cache
         # shapes keep SDPA
-        if (
-            kv_cache is None
-            and q.is_cuda
-            and q.dtype == torch.bfloat16
-            and self.head_dim == 128
-            and T % 128 == 0
-            and not os.environ.get("RAY_AMD_ATTN_SDPA")
-        ):
+        if flash(q):
             out = ops.flash_attention(q, k, v, causal=True)
         else:
             out = F.scaled_dot_product_attention(
@@ -169,6 +181,20 @@ class Block(nn.Module):
         x = x + self.mlp(self.mlp_norm(x))
         return x
 
+    def forward_carried(self, x, delta, cosT, sinT):
+        """Training path of LlamaModel: the block's last residual add is left
+        to the next norm. Takes and returns (x, delta) with the block's
+        input / output being x + delta (delta None: x itself); every norm
+        that follows an add is one ops.add_rmsnorm."""
+        if delta is None:
+            h = self.attn_norm(x)
+        else:
+            x, h = ops.add_rmsnorm(x, delta, self.attn_norm.weight,
+                                   self.attn_norm.eps)
+        x, h = ops.add_rmsnorm(x, self.attn(h, cosT, sinT),
+                               self.mlp_norm.weight, self.mlp_norm.eps)
+        return x, self.mlp(h)
+
 
 class LlamaModel(nn.Module):
     def __init__(self, cfg: LlamaConfig, dtype=torch.bfloat16,
@@ -200,15 +226,28 @@ class LlamaModel(nn.Module):
 
     def forward(self, tokens, targets=None, kv_caches=None, pos0: int = 0):
         x = self.embed(tokens)
-        for i, layer in enumerate(self.layers):
-            cache = kv_caches[i] if kv_caches is not None else None
-            if self.gradient_checkpointing and self.training:
-                x = torch.utils.checkpoint.checkpoint(
-                    layer, x, self.cosT, self.sinT, use_reentrant=False
-                )
-            else:
-                x = layer(x, self.cosT, self.sinT, cache, pos0)
-        x = self.final_norm(x)
+        carried = (ops._FUSED_ADD_NORM and kv_caches is None and pos0 == 0
+                   and len(self.layers) > 0
+                   and not (self.gradient_checkpointing and self.training))
+        if carried:
+            # (x, delta): each block leaves its last residual add to the
+            # norm that follows it
+            delta = None
+            for layer in self.layers:
+                x, delta = layer.forward_carried(x, delta, self.cosT,
+                                                 self.sinT)
+            _, x = ops.add_rmsnorm(x, delta, self.final_norm.weight,
+                                   self.final_norm.eps)
+        else:
+            for i, layer in enumerate(self.layers):
+                cache = kv_caches[i] if kv_caches is not None else None
+                if self.gradient_checkpointing and self.training:
+                    x = torch.utils.checkpoint.checkpoint(
+                        layer, x, self.cosT, self.sinT, use_reentrant=False
+                    )
+                else:
+                    x = layer(x, self.cosT, self.sinT, cache, pos0)
+            x = self.final_norm(x)
         if targets is not None:
             if x.is_cuda and os.environ.get("RAY_AMD_CHUNKED_CE"):
                 # opt-in chunked fused lm_head+CE: saves ~15 GB peak

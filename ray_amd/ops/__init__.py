@@ -66,6 +66,46 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5):
     return _RMSNorm.apply(x, w, eps)
 
 
+# test hook: False sends LlamaModel's training path back to separate
+# residual adds and norms (for monkeypatch, like _WGRAD_FORCE)
+_FUSED_ADD_NORM = True
+
+
+class _AddRMSNorm(torch.autograd.Function):
+    """s = x + r and h = rmsnorm(s), one forward kernel. Backward is one
+    call: the norm's dx with the gradient of s added in the kernel's store
+    (rounded as the bf16 add of the two tensors), which is the gradient of
+    both x and r."""
+
+    @staticmethod
+    def forward(ctx, x, r, w, eps):
+        _require_ext("add_rmsnorm")
+        ctx.set_materialize_grads(False)
+        w = w.contiguous()
+        s, h, inv = _K.add_rmsnorm_fwd(x.contiguous(), r.contiguous(), w, eps)
+        ctx.save_for_backward(s, w, inv)
+        return s, h
+
+    @staticmethod
+    def backward(ctx, g_s, g_h):
+        if g_h is None:
+            return g_s, g_s, None, None
+        s, w, inv = ctx.saved_tensors
+        dx, dw = _K.rmsnorm_bwd_res(
+            g_h.contiguous(), s, w, inv,
+            None if g_s is None else g_s.contiguous())
+        return dx, dx, dw.to(w.dtype), None
+
+
+def add_rmsnorm(x: torch.Tensor, r: torch.Tensor, w: torch.Tensor,
+                eps: float = 1e-5):
+    """(s, h) with s = x + r and h = rmsnorm(s, w, eps)."""
+    if not x.is_cuda:
+        s = x + r
+        return s, rmsnorm(s, w, eps)
+    return _AddRMSNorm.apply(x, r, w, eps)
+
+
 class RMSNorm(torch.nn.Module):
     def __init__(self, dim: int, eps: float = 1e-5, dtype=torch.bfloat16):
         super().__init__()
@@ -643,22 +683,35 @@ def flash_attention_ref(q, k, v, causal=True):
     return out.to(q.dtype), lse
 
 
-def _is_bthd_view(t):
+def _is_bthd_view(t, wide=False):
     """[B,H,T,D] tensor that is a transpose view of [B,T,H,D] storage
     (the model's natural post-RoPE layout) — the kernels read it
-    directly, no transpose-contiguous copy."""
+    directly, no transpose-contiguous copy. With `wide`, the token row may
+    be wider than H*D: strides (T*rs, D, rs, 1) with rs >= H*D, as the q,
+    k and v column sections of one packed [B,T,(Hq+2Hkv)*D] GEMM output
+    have. A wider row must keep every head vector 16-byte aligned
+    (rs % 8 == 0 and an aligned start) and inside the kernels' 32-bit
+    staging offsets (the same bounds as csrc/ops.hip attn_layout)."""
     B, H, T, D = t.shape
     st = t.stride()
-    return (st[3] == 1 and st[1] == D and st[2] == H * D
-            and st[0] == H * T * D)
+    rs = st[2]
+    if not (st[3] == 1 and st[1] == D and st[0] == T * rs):
+        return False
+    if rs == H * D:
+        return True
+    return (wide and rs > H * D and rs % 8 == 0
+            and t.data_ptr() % 16 == 0
+            and T * rs < 2 ** 31 and 64 * rs < 2 ** 30)
 
 
 def _attn_operands(q, k, v):
     """q, k, v in a layout the kernels read, and whether that is the BTHD
     view: the tensors as they are if T % 256 == 0 and all three are BTHD
-    views (only the 256-row kernels read those), else contiguous copies."""
-    if q.shape[2] % 256 == 0 and _is_bthd_view(q) and _is_bthd_view(k) \
-            and _is_bthd_view(v):
+    views, wide rows included, k and v at one row stride (only the 256-row
+    kernels read those), else contiguous copies."""
+    if q.shape[2] % 256 == 0 and _is_bthd_view(q, True) \
+            and _is_bthd_view(k, True) and _is_bthd_view(v, True) \
+            and k.stride(2) == v.stride(2):
         return q, k, v, True
     return q.contiguous(), k.contiguous(), v.contiguous(), False
 
@@ -731,6 +784,93 @@ def flash_attention(q, k, v, causal: bool = True, q_offset: int = 0,
         lse = r[1][:, :, :T] if pad else r[1]
         return out, lse
     return out
+
+
+# test hook: False sends Attention.forward back to split + rope + flash
+# attention (for monkeypatch, like _WGRAD_FORCE)
+_FUSED_QKV_ATTN = True
+
+
+def _qkv_sections(qkv, n_heads, n_kv_heads):
+    """The q, k, v column sections of packed [B,T,(Hq+2Hkv)*D] as
+    [B,H,T,D] views."""
+    B, T, W = qkv.shape
+    D = W // (n_heads + 2 * n_kv_heads)
+    q, k, v = qkv.split([n_heads * D, n_kv_heads * D, n_kv_heads * D], dim=-1)
+    return (q.view(B, T, n_heads, D).transpose(1, 2),
+            k.view(B, T, n_kv_heads, D).transpose(1, 2),
+            v.view(B, T, n_kv_heads, D).transpose(1, 2))
+
+
+def _qkv_packed_ok(qkv, n_heads, n_kv_heads):
+    """Whether the fused path reads this packed buffer as it is."""
+    if not (_K is not None and qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and qkv.dim() == 3 and qkv.shape[1] % 256 == 0
+            and qkv.shape[2] == (n_heads + 2 * n_kv_heads) * 128
+            and n_heads % n_kv_heads == 0
+            and qkv.stride(2) == 1
+            and qkv.stride(0) == qkv.shape[1] * qkv.stride(1)
+            and not qkv._is_view()):
+        return False
+    return all(_is_bthd_view(t, True)
+               for t in _qkv_sections(qkv, n_heads, n_kv_heads))
+
+
+class _QkvRopeAttn(torch.autograd.Function):
+    """RoPE in place on the q and k sections of the packed projection
+    output, flash attention on the three section views; backward writes
+    dq, dk, dv into one packed buffer and un-rotates it in place."""
+
+    @staticmethod
+    def forward(ctx, qkv, cosT, sinT, n_heads, n_kv_heads):
+        ctx.set_materialize_grads(False)
+        _K.rope_qk_inplace(qkv, cosT, sinT, n_heads, n_kv_heads, 1)
+        ctx.mark_dirty(qkv)
+        q, k, v = _qkv_sections(qkv, n_heads, n_kv_heads)
+        out, lse = _K.flash_attn_fwd(q, k, v, True, 0, True)
+        ctx.save_for_backward(qkv, out, lse, cosT, sinT)
+        ctx.heads = (n_heads, n_kv_heads)
+        # a tensor written in place has to be an output as well
+        return out, qkv
+
+    @staticmethod
+    def backward(ctx, d_out, d_rot):
+        qkv, out, lse, cosT, sinT = ctx.saved_tensors
+        n_heads, n_kv_heads = ctx.heads
+        if d_rot is not None:
+            raise NotImplementedError(
+                "qkv_rope_attention: the rotated buffer is not an output")
+        q, k, v = _qkv_sections(qkv, n_heads, n_kv_heads)
+        if not _is_bthd_view(d_out):
+            d_out = d_out.transpose(1, 2).contiguous().transpose(1, 2)
+        d_qkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+        _K.flash_attn_bwd(q, k, v, out, d_out, lse, True, d_qkv)
+        _K.rope_qk_inplace(d_qkv, cosT, sinT, n_heads, n_kv_heads, -1)
+        return d_qkv, None, None, None, None
+
+
+def qkv_rope_attention(qkv, cosT, sinT, n_heads, n_kv_heads):
+    """Causal self-attention from the packed projection output
+    qkv [B,T,(Hq+2Hkv)*D] (q heads, k heads, v heads along the last
+    dimension) with RoPE on q and k; returns [B,T,Hq*D]. On the GPU, for
+    bf16, D == 128 and T % 256 == 0, qkv is rotated IN PLACE and the
+    kernels read and write the packed layout; anything else runs split,
+    `rope` and `flash_attention`."""
+    B, T, W = qkv.shape
+    D = W // (n_heads + 2 * n_kv_heads)
+    cosT, sinT = cosT[:T], sinT[:T]
+    if (_FUSED_QKV_ATTN and _qkv_packed_ok(qkv, n_heads, n_kv_heads)
+            and cosT.is_contiguous() and sinT.is_contiguous()
+            and cosT.data_ptr() % 16 == 0 and sinT.data_ptr() % 16 == 0):
+        out, _ = _QkvRopeAttn.apply(qkv, cosT, sinT, n_heads, n_kv_heads)
+        return out.transpose(1, 2).reshape(B, T, n_heads * D)
+    q, k, v = qkv.split([n_heads * D, n_kv_heads * D, n_kv_heads * D], dim=-1)
+    v = v.reshape(B, T, n_kv_heads, D)
+    q = rope(q.view(B, T, n_heads, D), cosT, sinT).transpose(1, 2)
+    k = rope(k.view(B, T, n_kv_heads, D), cosT, sinT).transpose(1, 2)
+    v = v.contiguous().transpose(1, 2)
+    out = flash_attention(q, k, v, causal=True)
+    return out.transpose(1, 2).reshape(B, T, n_heads * D)
 
 
 # --------------------------------------------------------------------------
