@@ -1,9 +1,10 @@
 // Tile math shared by the attention kernels: fragment types, the two
 // cvt_pk forms, the K swizzle, S' = K·Q^T, the online-softmax step and
-// P·V. The forward kernels (flash_attn_v5.hip, flash_attn_v6.hip,
-// paged_attn_prefill.hip) call all of it; the backward kernels take the
-// types and conversions. Staging, prologues and epilogues stay with the
-// kernels: that is where they differ.
+// P·V. flash_attn_v5.hip and paged_attn_prefill.hip call s_tile,
+// softmax_step and pv_tile; flash_attn_v7.hip calls the two-phase form of
+// the same arithmetic at the end of this file; the backward kernels take
+// the types and conversions. Staging, prologues and epilogues stay with
+// the kernels: that is where they differ.
 //
 // Swapped-operand form: S' = K·Q^T puts S'[k][q] in C layout with
 // q = lane&31, so a lane owns ONE query column. The softmax max/sum over
@@ -186,6 +187,164 @@ DEV_INLINE void pv_tile(f32x16 p, const short (&v_tile)[ROWS][D], int kt,
           __builtin_bit_cast(bf16x8, *reinterpret_cast<short8*>(vtmp));
       o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb, o_acc[dt],
                                                           0, 0, 0);
+    }
+  }
+}
+
+// ---- Two-phase form of the same tile math (flash_attn_v7.hip) ----
+//
+// The pieces above run S, softmax and P·V of a sub-tile back to back. The
+// pieces below cut the same arithmetic, operation for operation, into a
+// VALU phase (softmax_pack: scores -> packed P, no LDS access) and a
+// matrix phase (pv_sub, s_sub: every MFMA and every LDS read), so that the
+// two waves of a SIMD can run the two phases against each other. K and V
+// are read from the [64][128] image of fa_bwd_lds_layout.h (fb6_off).
+
+// Transposed-read base of pv_sub: the 4 rows 16kc + 8hi + 4h .. +3 of a
+// 32-row sub-tile, columns 32dt + 16grp16 .. +15, sit at
+// fa_pv_tbase(lane, h) + 2048kc + 256dt of the sub-tile's image. The lane
+// halves take rows 8hi .. 8hi+7 of each 16-key chunk, as pv_tile does, so
+// the MFMA sees the same operands in the same k slots; fb6_tbase's row
+// assignment (4hi and 8 + 4hi) belongs to the backward kernels' permuted
+// fragments.
+DEV_INLINE int fa_pv_tbase(int lane, int h) {
+  const int gl = lane & 15;
+  const int grp16 = (lane >> 4) & 1;
+  const int hi = lane >> 5;
+  return 1024 * hi + 32 * (4 * h + (gl >> 2)) +
+         8 * ((2 * grp16 + ((gl & 3) >> 1)) ^ ((2 * hi + h) & 3)) +
+         4 * (gl & 1);
+}
+
+// S' = K·Q^T of one 32-key sub-tile whose image starts at k_img; rb0 and
+// rb1 are fb6_rbase(lane, 0 / 1). All 8 fragments are read before the
+// chain, so no MFMA waits on the read issued just in front of it.
+DEV_INLINE f32x16 s_sub(const short* k_img, int rb0, int rb1,
+                        const bf16x8 (&q_frag)[8]) {
+  bf16x8 kf[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+    kf[c] = ld8(k_img + ((c & 1) ? rb1 : rb0) + 256 * (c >> 1));
+  f32x16 acc{};
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c], q_frag[c], acc, 0,
+                                                  0, 0);
+  return acc;
+}
+
+// x of the partner lane (l ^ 32) combined with the lane's own by max / by
+// sum, through one v_permlane32_swap instead of a ds_bpermute round trip
+// through the LDS pipe. a keeps the low half's x in both halves, b the
+// high half's; max and + are commutative, so the result has the bits of
+// fmaxf(x, __shfl_xor(x, 32)) and of x + __shfl_xor(x, 32).
+DEV_INLINE void halves32(float x, float& a, float& b) {
+  const unsigned u = __builtin_bit_cast(unsigned, x);
+  auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  a = __builtin_bit_cast(float, (unsigned)sw[0]);
+  b = __builtin_bit_cast(float, (unsigned)sw[1]);
+}
+
+// softmax_step without the O rescale, followed by pv_tile's packing:
+// s_acc -> the two B fragments of P (16 keys each). m_run and l_run are
+// updated; `need` and `sc` tell the caller to multiply O by sc before this
+// sub-tile's P·V (and after the previous one's). MASKED = false is
+// softmax_step's full_tile arm; MASKED = true applies the k_lim and causal
+// masks by select, which leaves an unmasked score as it is.
+template <bool MASKED>
+DEV_INLINE void softmax_pack(f32x16 s_acc, float& m_run, float& l_run,
+                             int k0s, int k_lim, int causal, int gq,
+                             float scale, int hi, bf16x8 (&pb)[2],
+                             bool& need, float& sc_out) {
+  const float THR = 8.f;
+  const float L2E = 1.4426950408889634f;
+  f32x16 p = s_acc * scale;
+  float rmax = -INFINITY;
+  if (!MASKED) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rmax = fmaxf(rmax, p[r]);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
+      int gk = k0s + krow;
+      bool masked = (gk >= k_lim) || (causal && gk > gq);
+      p[r] = masked ? -INFINITY : p[r];
+      rmax = fmaxf(rmax, p[r]);
+    }
+  }
+  {
+    float a, b;
+    halves32(rmax, a, b);
+    rmax = fmaxf(a, b);
+  }
+  bool need_rescale = (m_run == -INFINITY) || (rmax - m_run > THR);
+  float m_new = need_rescale ? fmaxf(m_run, rmax) : m_run;
+  float sc = 1.f;
+  if (need_rescale)
+    sc = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
+  if (m_new == -INFINITY) sc = 0.f;
+  float mb = m_new * L2E;
+  float psum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    p[r] = (m_new == -INFINITY)
+               ? 0.f
+               : __builtin_amdgcn_exp2f(__builtin_fmaf(p[r], L2E, -mb));
+    psum += p[r];
+  }
+  {
+    float a, b;
+    halves32(psum, a, b);
+    psum = a + b;
+  }
+  l_run = l_run * sc + psum;
+  m_run = m_new;
+  need = need_rescale;
+  sc_out = sc;
+#pragma unroll
+  for (int kc = 0; kc < 2; ++kc) {
+    unsigned int a0 = cvt_pk_asm(p[8 * kc + 0], p[8 * kc + 1]);
+    unsigned int a1 = cvt_pk_asm(p[8 * kc + 2], p[8 * kc + 3]);
+    unsigned int b0 = cvt_pk_asm(p[8 * kc + 4], p[8 * kc + 5]);
+    unsigned int b1 = cvt_pk_asm(p[8 * kc + 6], p[8 * kc + 7]);
+    auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+    auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+    u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
+             (unsigned)sw1[1]};
+    pb[kc] = __builtin_bit_cast(bf16x8, pw);
+  }
+}
+
+// O' *= sc on the lanes whose running max moved (softmax_step's tail).
+DEV_INLINE void o_rescale(f32x16 (&o_acc)[4], bool need, float sc) {
+  if (need) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o_acc[d][r] *= sc;
+  }
+}
+
+// O' += V^T·P of one 32-key sub-tile whose image starts at v_img; tb0 and
+// tb1 are fa_pv_tbase(lane, 0 / 1). Sums kc then dt, as pv_tile does.
+DEV_INLINE void pv_sub(const bf16x8 (&pb)[2], const short* v_img, int tb0,
+                       int tb1, f32x16 (&o_acc)[4]) {
+#pragma unroll
+  for (int kc = 0; kc < 2; ++kc) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const int o = 2048 * kc + 256 * dt;
+      short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) short4v*)(v_img + tb0 + o));
+      short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) short4v*)(v_img + tb1 + o));
+      short vtmp[8] = {lo[0], lo[1], lo[2], lo[3],
+                       hi4[0], hi4[1], hi4[2], hi4[3]};
+      bf16x8 va =
+          __builtin_bit_cast(bf16x8, *reinterpret_cast<short8*>(vtmp));
+      o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb[kc],
+                                                          o_acc[dt], 0, 0, 0);
     }
   }
 }

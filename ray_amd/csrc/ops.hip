@@ -9,12 +9,12 @@
 #include "hip/rl_scans.hip"
 #include "hip/cross_entropy.hip"
 // Flash attention has two paths, chosen from the shape alone:
-//   T % 256 == 0: 256-row kernels (fwd v6, dq v5, dkv v6), which read
+//   T % 256 == 0: 256-row kernels (fwd v7, dq v5, dkv v6), which read
 //                 contiguous BHTD or BTHD-view tensors;
 //   otherwise:    128-row kernels (fwd v5, dq/dv/dk v3), contiguous BHTD.
 // Each file below compiles on its own.
 #include "hip/flash_attn_v5.hip"
-#include "hip/flash_attn_v6.hip"
+#include "hip/flash_attn_v7.hip"
 #include "hip/fa_bwd_prep.hip"
 #include "hip/fa_bwd_v3.hip"
 #include "hip/fa_bwd_dq_v5.hip"
@@ -882,8 +882,8 @@ std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k,
   short* op = (short*)o.data_ptr();
   const int c = causal ? 1 : 0, qo = (int)q_offset;
   if (T % 256 == 0)
-    // 256 query rows per block: 8-wave dbuf/async-stage/swizzled structure
-    hipLaunchKernelGGL(flash_attn_fwd_v6_bf16, dim3(T / 256, B * Hq),
+    // 256 query rows per block: 8 waves on the two-phase ping-pong schedule
+    hipLaunchKernelGGL(flash_attn_fwd_v7_bf16, dim3(T / 256, B * Hq),
                        dim3(512), 0, cur_stream(), qp, kp, vp, op, lse_ptr,
                        B, Hq, Hkv, T, Tk, c, qo, scale, bthd, (int)q_rs,
                        (int)o_rs, (int)k_rs);

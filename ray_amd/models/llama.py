@@ -136,9 +136,8 @@ class Attention(nn.Module):
             k, v = kv_cache.update(k, v, pos0)
         is_causal = kv_cache is None or T > 1
         # training self-attention runs the hand-written CDNA4 flash
-        # kernels (fwd v6 + fa_bwd v4: measured at parity with AOTriton
-        # round-trip, profiles/flash_attn_v6_bench.log); decode/cache
-        # shapes keep SDPA
+        # kernels (ray_amd/csrc/ops.hip names the current set; timings
+        # in PERFORMANCE.md); decode/cache shapes keep SDPA
         if flash(q):
             out = ops.flash_attention(q, k, v, causal=True)
         else:
