@@ -31,9 +31,13 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
   __shared__ __attribute__((aligned(16))) short k_lds[2 * FB5_KT * FB3_D];
   __shared__ __attribute__((aligned(16))) short v_lds[2 * FB5_KT * FB3_D];
 
-  // heaviest causal block (the last query rows) first: the light blocks
-  // fill the tail of the grid
-  const int q0 = (gridDim.x - 1 - blockIdx.x) * 256;
+  // heaviest causal block (the last query rows) first inside a grid row,
+  // and the order rotated from row to row: workgroups are dealt to the 8
+  // XCDs round-robin, so with gridDim.x a multiple of 8 and a fixed order
+  // one XCD gets the heaviest block of every head (PERFORMANCE.md). A
+  // head's blocks stay together in time and share K/V in the L2.
+  const int qb = (blockIdx.x + blockIdx.y) % gridDim.x;
+  const int q0 = (gridDim.x - 1 - qb) * 256;
   const int bh = blockIdx.y;
   const int b = bh / Hq;
   const int hq = bh % Hq;
