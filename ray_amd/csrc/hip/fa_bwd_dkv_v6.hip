@@ -233,6 +233,7 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
       const bool full_tile = !causal || (k0 + 32 * wave + 31 <= qts);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // c_row spelled out: the call changes this loop's code
         const int gq = qts + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float pv = __builtin_amdgcn_exp2f(s_acc[r] * c2);
         if (!full_tile && gk > gq) pv = 0.f;
@@ -260,6 +261,7 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dkv_v6_bf16(
       for (int s = 0; s < 2; ++s) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
+          // ld_tr8 spelled out: dO's and Q's reads are issued in pairs
           short dtmp[8], qtmp[8];
 #pragma unroll
           for (int h = 0; h < 2; ++h) {

@@ -159,31 +159,25 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
         }
       }
 
-      float ds[16];
+      f32x16 ds;
       const bool full_tile = !causal || (k0 + 31 <= q0 + wave * 32);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // c_row spelled out: the call changes this loop's code
         const int gk = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float p = __builtin_amdgcn_exp2f(s_acc[r] * c2);
         if (!full_tile && gk > my_q) p = 0.f;
         ds[r] = p * dp_acc[r] * scale;
       }
 
-      // dQ += dS·K: A = dS via cvt_pk + permlane32_swap, B = K via
-      // ds_read_tr16_b64
+      // dQ += dS·K: A = dS via pack_swap (plain cvt_pk, see fa_tile.h),
+      // B = K via ds_read_tr16_b64
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const unsigned int a0 = cvt_pk(ds[8 * s + 0], ds[8 * s + 1]);
-        const unsigned int a1 = cvt_pk(ds[8 * s + 2], ds[8 * s + 3]);
-        const unsigned int b0 = cvt_pk(ds[8 * s + 4], ds[8 * s + 5]);
-        const unsigned int b1 = cvt_pk(ds[8 * s + 6], ds[8 * s + 7]);
-        auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
-                     (unsigned)sw1[1]};
-        const bf16x8 af = __builtin_bit_cast(bf16x8, pw);
+        const bf16x8 af = pack_swap<false>(ds, s);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
+          // ld_tr8 spelled out: the call changes this loop's code
           short ktmp[8];
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
@@ -212,13 +206,6 @@ extern "C" __global__ __launch_bounds__(512) void fa_bwd_dq_v5_bf16(
 #undef FB5_DQ_LOAD
 #undef FB5_DQ_WRITE
 
-  short* out = dQ + dqbase + (long long)wave * 32 * dq_rs;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int qrow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      out[(long long)qrow * dq_rs + 32 * dt + (lane & 31)] =
-          f2bf(dq_acc[dt][r]);
-    }
+  c_store(dq_acc, dQ + dqbase + (long long)wave * 32 * dq_rs, dq_rs, lane,
+          hi);
 }

@@ -19,17 +19,26 @@
 #include "fa_bwd_frag.h"
 
 // ---------------------------------------------------------------------
-// dV: grid (T/128, B*Hkv); 4 waves x 32 kv rows; K in registers,
-// dV accumulates in registers. dv[k][d] = sum_q P^T[k][q] dO[q][d]
+// dK (DK = true) or dV (DK = false) of 128 key rows: grid (T/128, B*Hkv),
+// 4 waves x 32 kv rows; K in registers, the output accumulates in
+// registers.
+//   dv[k][d] = sum_q P^T[k][q] dO[q][d]
+//   dk[k][d] = sum_q dS̃^T[k][q] Q[q][d]
+// dK also holds V in registers for dP^T = V·dO^T and stages Dsum; its
+// second product reads q_lds where dV's reads do_lds. Two kernels, not
+// one, so that each fits 2 waves/SIMD.
 // ---------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
+template <bool DK>
+__global__ __launch_bounds__(256) void fa_bwd_dkv_v3_bf16(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
-    const float* __restrict__ LSE, short* __restrict__ dV, int B, int Hq,
-    int Hkv, int T, int causal, float scale) {
+    const float* __restrict__ LSE, const float* __restrict__ Dsum,
+    short* __restrict__ dKV, int B, int Hq, int Hkv, int T, int causal,
+    float scale) {
   __shared__ short q_lds[2][FB3_QT][FB3_D];
   __shared__ short do_lds[2][FB3_QT][FB3_D];
   __shared__ float lse_lds[2][FB3_QT];
+  __shared__ float dsum_lds[2][FB3_QT];  // DK only: unused, it costs no LDS
   __shared__ short scratch[4][32][40];
 
   const int k0 = blockIdx.x * 128;
@@ -43,46 +52,65 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
   const int a_off = 8 * hi;
 
   const long long kbase = (((long long)b * Hkv + hkv) * T + k0) * FB3_D;
-  // K register-resident: only this wave's own 32 rows are ever read
-  bf16x8 k_frag[8];
+  // K (and V) register-resident: only this wave's own 32 rows are ever read
+  bf16x8 k_frag[8], v_frag[8];
   {
     const short* kp = K + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
+    const short* vp = V + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) k_frag[c] = ld8(kp + 16 * c + a_off);
+    for (int c = 0; c < 8; ++c) {
+      k_frag[c] = ld8(kp + 16 * c + a_off);
+      if constexpr (DK) v_frag[c] = ld8(vp + 16 * c + a_off);
+    }
   }
 
-  f32x16 dv_acc[4];
+  f32x16 acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) dv_acc[t] = f32x16{};
+  for (int t = 0; t < 4; ++t) acc[t] = f32x16{};
   const float L2E = 1.4426950408889634f;
 
   const int q_start = causal ? k0 : 0;
   const int nq = (T - q_start + FB3_QT - 1) / FB3_QT;
   const int n_tiles = rep * nq;
 
-  // staging regs: 64 rows x 16 chunks / 256 threads = 4 chunks/tensor
+  // Staging of tile t_idx of the flattened (head, q-tile) sequence: 64 rows
+  // x 16 chunks / 256 threads = 4 chunks per tensor; chunk j of a thread is
+  // row r, columns c .. c+7 of the tile.
+#define FB3_TILE_BASE(t_idx)                                              \
+  const int g_ = (t_idx) / nq;                                            \
+  const int q0_ = q_start + ((t_idx) % nq) * FB3_QT;                      \
+  const int hq_ = hkv * rep + g_;                                         \
+  const long long qb_ = (((long long)b * Hq + hq_) * T) * FB3_D;          \
+  const long long lb_ = ((long long)b * Hq + hq_) * T;
+#define FB3_CHUNK(j)                                                      \
+  int i = threadIdx.x + 256 * (j);                                        \
+  int r = i >> 4;                                                         \
+  int c = (i & 15) * 8;
+  // global -> qv, dv (zero past T)
+#define FB3_CHUNK_LOAD(j)                                                 \
+  FB3_CHUNK(j)                                                            \
+  int qrow = q0_ + r;                                                     \
+  short8 qv{0, 0, 0, 0, 0, 0, 0, 0}, dv{0, 0, 0, 0, 0, 0, 0, 0};          \
+  if (qrow < T) {                                                         \
+    qv = *reinterpret_cast<const short8*>(qb_ + Q +                       \
+                                          (long long)qrow * FB3_D + c);   \
+    dv = *reinterpret_cast<const short8*>(qb_ + dO +                      \
+                                          (long long)qrow * FB3_D + c);   \
+  }
+#define FB3_CHUNK_WRITE(buf, qv_, dv_)                                    \
+  int csw = c ^ ((r & 7) << 3);                                           \
+  *reinterpret_cast<short8*>(&q_lds[buf][r][csw]) = qv_;                  \
+  *reinterpret_cast<short8*>(&do_lds[buf][r][csw]) = dv_;
+
+  // dV stages through registers: the next tile's global loads are issued
+  // before this tile's compute (LOAD) and written after it (WRITE).
   short8 q_stage[4], do_stage[4];
   float lse_stage = 0.f;
-
 #define FB3_DV_LOAD(t_idx)                                                \
   do {                                                                    \
-    const int g_ = (t_idx) / nq;                                          \
-    const int q0_ = q_start + ((t_idx) % nq) * FB3_QT;                    \
-    const int hq_ = hkv * rep + g_;                                       \
-    const long long qb_ = (((long long)b * Hq + hq_) * T) * FB3_D;        \
-    const long long lb_ = ((long long)b * Hq + hq_) * T;                  \
+    FB3_TILE_BASE(t_idx)                                                  \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) {                       \
-      int i = threadIdx.x + 256 * j;                                      \
-      int r = i >> 4;                                                     \
-      int c = (i & 15) * 8;                                               \
-      int qrow = q0_ + r;                                                 \
-      short8 qv{0, 0, 0, 0, 0, 0, 0, 0}, dv{0, 0, 0, 0, 0, 0, 0, 0};      \
-      if (qrow < T) {                                                     \
-        qv = *reinterpret_cast<const short8*>(qb_ + Q +                   \
-                                              (long long)qrow * FB3_D + c); \
-        dv = *reinterpret_cast<const short8*>(qb_ + dO +                  \
-                                              (long long)qrow * FB3_D + c); \
-      }                                                                   \
+      FB3_CHUNK_LOAD(j)                                                   \
       q_stage[j] = qv;                                                    \
       do_stage[j] = dv;                                                   \
     }                                                                     \
@@ -91,147 +119,14 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dv_v3_bf16(
       lse_stage = (qrow < T) ? LSE[lb_ + qrow] : INFINITY;                \
     }                                                                     \
   } while (0)
-
 #define FB3_DV_WRITE(buf)                                                 \
   do {                                                                    \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) {                       \
-      int i = threadIdx.x + 256 * j;                                      \
-      int r = i >> 4;                                                     \
-      int c = (i & 15) * 8;                                               \
-      int csw = c ^ ((r & 7) << 3);                                       \
-      *reinterpret_cast<short8*>(&q_lds[buf][r][csw]) = q_stage[j];       \
-      *reinterpret_cast<short8*>(&do_lds[buf][r][csw]) = do_stage[j];     \
+      FB3_CHUNK(j)                                                        \
+      FB3_CHUNK_WRITE(buf, q_stage[j], do_stage[j])                       \
     }                                                                     \
     if (threadIdx.x < FB3_QT) lse_lds[buf][threadIdx.x] = lse_stage;      \
   } while (0)
-
-  FB3_DV_LOAD(0);
-  FB3_DV_WRITE(0);
-  __syncthreads();
-
-  for (int t = 0; t < n_tiles; ++t) {
-    const int cur = t & 1;
-    const int q0s = q_start + (t % nq) * FB3_QT;
-    if (t + 1 < n_tiles) FB3_DV_LOAD(t + 1);
-
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      const int qts = q0s + 32 * qt;
-      if (qts >= T) break;
-      if (causal && k0 + 32 * wave > qts + 31) continue;
-
-      f32x16 s_acc{};
-      {
-        const int rr = 32 * qt + (lane & 31);
-        const short* qrow = &q_lds[cur][rr][0];
-        const int sw = (rr & 7) << 3;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          // S'^T tile: A = this wave's K rows (regs), B = Q^T from LDS
-          bf16x8 qf = ld8(qrow + ((16 * c + a_off) ^ sw));
-          s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_frag[c], qf,
-                                                          s_acc, 0, 0, 0);
-        }
-      }
-      // C layout: col = lane&31 = q (this lane's loaded q row),
-      // rows = this wave's k
-      const int gq = qts + (lane & 31);
-      const float lse_q = lse_lds[cur][32 * qt + (lane & 31)];
-      const bool full_tile = !causal || (k0 + 32 * wave + 31 <= qts);
-      short(*scr)[40] = scratch[wave];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int gk = k0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        float pv = __builtin_amdgcn_exp2f(
-            __builtin_fmaf(s_acc[r] * scale, L2E, -lse_q * L2E));
-        if (!full_tile && gk > gq) pv = 0.f;
-        scr[(r & 3) + 8 * (r >> 2) + 4 * hi][lane & 31] = f2bf(pv);
-      }
-      __builtin_amdgcn_s_waitcnt(0);
-#pragma unroll
-      for (int qc = 0; qc < 2; ++qc) {
-        bf16x8 af = __builtin_bit_cast(
-            bf16x8, *reinterpret_cast<const short8*>(
-                            &scr[lane & 31][16 * qc + a_off]));
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          short dtmp[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            int row = 32 * qt + 16 * qc + a_off + i;
-            int col = 32 * dt + (lane & 31);
-            dtmp[i] = do_lds[cur][row][col ^ ((row & 7) << 3)];
-          }
-          bf16x8 bf = __builtin_bit_cast(
-              bf16x8, *reinterpret_cast<short8*>(dtmp));
-          dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              af, bf, dv_acc[dt], 0, 0, 0);
-        }
-      }
-    }
-
-    if (t + 1 < n_tiles) FB3_DV_WRITE(cur ^ 1);
-    __syncthreads();
-  }
-
-  short* outv = dV + kbase + (long long)wave * 32 * FB3_D;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      outv[(long long)krow * FB3_D + 32 * dt + (lane & 31)] =
-          f2bf(dv_acc[dt][r]);
-    }
-}
-
-// ---------------------------------------------------------------------
-// dK: same structure; V also register-resident; needs Dsum and
-// dP^T = V·dO^T.  dk[k][d] = sum_q dS̃^T[k][q] Q[q][d]
-// ---------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
-    const short* __restrict__ Q, const short* __restrict__ K,
-    const short* __restrict__ V, const short* __restrict__ dO,
-    const float* __restrict__ LSE, const float* __restrict__ Dsum,
-    short* __restrict__ dK, int B, int Hq, int Hkv, int T, int causal,
-    float scale) {
-  __shared__ short q_lds[2][FB3_QT][FB3_D];
-  __shared__ short do_lds[2][FB3_QT][FB3_D];
-  __shared__ float lse_lds[2][FB3_QT];
-  __shared__ float dsum_lds[2][FB3_QT];
-  __shared__ short scratch[4][32][40];
-
-  const int k0 = blockIdx.x * 128;
-  const int bh = blockIdx.y;
-  const int b = bh / Hkv;
-  const int hkv = bh % Hkv;
-  const int rep = Hq / Hkv;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int hi = lane >> 5;
-  const int a_off = 8 * hi;
-
-  const long long kbase = (((long long)b * Hkv + hkv) * T + k0) * FB3_D;
-  bf16x8 k_frag[8], v_frag[8];
-  {
-    const short* kp = K + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
-    const short* vp = V + kbase + ((long long)32 * wave + (lane & 31)) * FB3_D;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      k_frag[c] = ld8(kp + 16 * c + a_off);
-      v_frag[c] = ld8(vp + 16 * c + a_off);
-    }
-  }
-
-  f32x16 dk_acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) dk_acc[t] = f32x16{};
-  const float L2E = 1.4426950408889634f;
-
-  const int q_start = causal ? k0 : 0;
-  const int nq = (T - q_start + FB3_QT - 1) / FB3_QT;
-  const int n_tiles = rep * nq;
-
   // dk holds K AND V register-resident plus the dK accumulators —
   // reg-staged async loads (like dv's) push it to 289 regs = 1
   // wave/SIMD (measured: the whole-bwd regression). Stage DIRECTLY
@@ -239,26 +134,10 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
   // liveness, still one barrier per 64-row tile.
 #define FB3_DK_STAGE(t_idx, buf)                                          \
   do {                                                                    \
-    const int g_ = (t_idx) / nq;                                          \
-    const int q0_ = q_start + ((t_idx) % nq) * FB3_QT;                    \
-    const int hq_ = hkv * rep + g_;                                       \
-    const long long qb_ = (((long long)b * Hq + hq_) * T) * FB3_D;        \
-    const long long lb_ = ((long long)b * Hq + hq_) * T;                  \
+    FB3_TILE_BASE(t_idx)                                                  \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) {                       \
-      int i = threadIdx.x + 256 * j;                                      \
-      int r = i >> 4;                                                     \
-      int c = (i & 15) * 8;                                               \
-      int csw = c ^ ((r & 7) << 3);                                       \
-      int qrow = q0_ + r;                                                 \
-      short8 qv{0, 0, 0, 0, 0, 0, 0, 0}, dv{0, 0, 0, 0, 0, 0, 0, 0};      \
-      if (qrow < T) {                                                     \
-        qv = *reinterpret_cast<const short8*>(qb_ + Q +                   \
-                                              (long long)qrow * FB3_D + c); \
-        dv = *reinterpret_cast<const short8*>(qb_ + dO +                  \
-                                              (long long)qrow * FB3_D + c); \
-      }                                                                   \
-      *reinterpret_cast<short8*>(&q_lds[buf][r][csw]) = qv;               \
-      *reinterpret_cast<short8*>(&do_lds[buf][r][csw]) = dv;              \
+      FB3_CHUNK_LOAD(j)                                                   \
+      FB3_CHUNK_WRITE(buf, qv, dv)                                        \
     }                                                                     \
     if (threadIdx.x < FB3_QT) {                                           \
       int qrow = q0_ + threadIdx.x;                                       \
@@ -267,13 +146,21 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
     }                                                                     \
   } while (0)
 
-  FB3_DK_STAGE(0, 0);
+  if constexpr (DK) {
+    FB3_DK_STAGE(0, 0);
+  } else {
+    FB3_DV_LOAD(0);
+    FB3_DV_WRITE(0);
+  }
   __syncthreads();
 
   for (int t = 0; t < n_tiles; ++t) {
     const int cur = t & 1;
     const int q0s = q_start + (t % nq) * FB3_QT;
-    if (t + 1 < n_tiles) FB3_DK_STAGE(t + 1, cur ^ 1);
+    if (t + 1 < n_tiles) {
+      if constexpr (DK) FB3_DK_STAGE(t + 1, cur ^ 1);
+      else FB3_DV_LOAD(t + 1);
+    }
 
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
@@ -289,29 +176,39 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
         const int sw = (rr & 7) << 3;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
+          // S'^T tile: A = this wave's K rows (regs), B = Q^T from LDS;
+          // dP^T likewise from V and dO^T
           bf16x8 qf = ld8(qrow + ((16 * c + a_off) ^ sw));
-          bf16x8 dof = ld8(dorow + ((16 * c + a_off) ^ sw));
+          bf16x8 dof;
+          if constexpr (DK) dof = ld8(dorow + ((16 * c + a_off) ^ sw));
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_frag[c], qf,
                                                           s_acc, 0, 0, 0);
-          dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_frag[c], dof,
-                                                           dp_acc, 0, 0, 0);
+          if constexpr (DK)
+            dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                v_frag[c], dof, dp_acc, 0, 0, 0);
         }
       }
+      // C layout: col = lane&31 = q (this lane's loaded q row),
+      // rows = this wave's k
       const int gq = qts + (lane & 31);
       const float lse_q = lse_lds[cur][32 * qt + (lane & 31)];
-      const float d_q = dsum_lds[cur][32 * qt + (lane & 31)];
+      float d_q = 0.f;
+      if constexpr (DK) d_q = dsum_lds[cur][32 * qt + (lane & 31)];
       const bool full_tile = !causal || (k0 + 32 * wave + 31 <= qts);
       short(*scr)[40] = scratch[wave];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // c_row spelled out: the call changes this loop's code
         int gk = k0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float pv = __builtin_amdgcn_exp2f(
             __builtin_fmaf(s_acc[r] * scale, L2E, -lse_q * L2E));
         if (!full_tile && gk > gq) pv = 0.f;
-        float dsv = pv * (dp_acc[r] - d_q) * scale;
-        scr[(r & 3) + 8 * (r >> 2) + 4 * hi][lane & 31] = f2bf(dsv);
+        if constexpr (DK) pv = pv * (dp_acc[r] - d_q) * scale;  // dS̃
+        scr[c_row(r, hi)][lane & 31] = f2bf(pv);
       }
       __builtin_amdgcn_s_waitcnt(0);
+      // second product: B = Q (dK) or dO (dV), gathered by column
+      const short(*src)[FB3_D] = DK ? q_lds[cur] : do_lds[cur];
 #pragma unroll
       for (int qc = 0; qc < 2; ++qc) {
         bf16x8 af = __builtin_bit_cast(
@@ -319,34 +216,45 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dk_v3_bf16(
                             &scr[lane & 31][16 * qc + a_off]));
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          short qtmp[8];
+          short tmp[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
             int row = 32 * qt + 16 * qc + a_off + i;
             int col = 32 * dt + (lane & 31);
-            qtmp[i] = q_lds[cur][row][col ^ ((row & 7) << 3)];
+            tmp[i] = src[row][col ^ ((row & 7) << 3)];
           }
           bf16x8 bf = __builtin_bit_cast(
-              bf16x8, *reinterpret_cast<short8*>(qtmp));
-          dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              af, bf, dk_acc[dt], 0, 0, 0);
+              bf16x8, *reinterpret_cast<short8*>(tmp));
+          acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              af, bf, acc[dt], 0, 0, 0);
         }
       }
     }
 
+    if constexpr (!DK) {
+      if (t + 1 < n_tiles) FB3_DV_WRITE(cur ^ 1);
+    }
     __syncthreads();
   }
+#undef FB3_TILE_BASE
+#undef FB3_CHUNK
+#undef FB3_CHUNK_LOAD
+#undef FB3_CHUNK_WRITE
+#undef FB3_DV_LOAD
+#undef FB3_DV_WRITE
+#undef FB3_DK_STAGE
 
-  short* outk = dK + kbase + (long long)wave * 32 * FB3_D;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      outk[(long long)krow * FB3_D + 32 * dt + (lane & 31)] =
-          f2bf(dk_acc[dt][r]);
-    }
+  c_store(acc, dKV + kbase + (long long)wave * 32 * FB3_D, FB3_D, lane, hi);
 }
+
+// the two instances ops.hip launches, so that this file emits them when
+// it is compiled on its own
+template __global__ void fa_bwd_dkv_v3_bf16<false>(
+    const short*, const short*, const short*, const short*, const float*,
+    const float*, short*, int, int, int, int, int, float);
+template __global__ void fa_bwd_dkv_v3_bf16<true>(
+    const short*, const short*, const short*, const short*, const float*,
+    const float*, short*, int, int, int, int, int, float);
 
 // ---------------------------------------------------------------------
 // dQ v3: grid (T/128, B*Hq), 4 waves x 32 q rows; 32-row K/V tiles
@@ -451,10 +359,11 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
         }
       }
 
-      float ds[16];
+      f32x16 ds;
       const bool full_tile = !causal || (k0 + 31 <= q0 + wave * 32);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // c_row spelled out: the call changes this loop's code
         int gk = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         float p = __builtin_amdgcn_exp2f(
             __builtin_fmaf(s_acc[r] * scale, L2E, -lse_q * L2E));
@@ -462,23 +371,16 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
         ds[r] = p * (dp_acc[r] - d_q) * scale;
       }
 
-      // dS A-fragments via cvt_pk+permlane (T12), then dQ += dS·K
+      // dS A-fragments via pack_swap, then dQ += dS·K
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc) {
-        unsigned int a0 = cvt_pk_asm(ds[8 * kc + 0], ds[8 * kc + 1]);
-        unsigned int a1 = cvt_pk_asm(ds[8 * kc + 2], ds[8 * kc + 3]);
-        unsigned int b0 = cvt_pk_asm(ds[8 * kc + 4], ds[8 * kc + 5]);
-        unsigned int b1 = cvt_pk_asm(ds[8 * kc + 6], ds[8 * kc + 7]);
-        auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
-                 (unsigned)sw1[1]};
-        bf16x8 af = __builtin_bit_cast(bf16x8, pw);
+        bf16x8 af = pack_swap<true>(ds, kc);
         {
           const int gl = lane & 15;
           const int grp16 = (lane >> 4) & 1;
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
+            // ld_tr8 spelled out: the call changes this loop's code
             short ktmp[8];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -502,6 +404,7 @@ extern "C" __global__ __launch_bounds__(256) void fa_bwd_dq_v3_bf16(
     __syncthreads();
   }
 
+  // c_store spelled out: the call changes the tile loop's code
   short* out = dQ + qbase + (long long)wave * 32 * q_rs;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)

@@ -2,9 +2,12 @@
 // cvt_pk forms, the K swizzle, S' = K·Q^T, the online-softmax step and
 // P·V. flash_attn_v5.hip and paged_attn_prefill.hip call s_tile,
 // softmax_step and pv_tile; flash_attn_v7.hip calls the two-phase form of
-// the same arithmetic at the end of this file; the backward kernels take
-// the types and conversions. Staging, prologues and epilogues stay with
-// the kernels: that is where they differ.
+// the same arithmetic at the end of this file. The backward kernels take
+// the types and conversions and the pieces that are the same in either
+// direction: c_row, the packed exchange of a C-layout tile (pack_swap),
+// the two-read transposed gather (ld_tr8) and the C-layout store of an
+// output tile (c_store). Staging, base-address prologues and the kernels'
+// own epilogues stay with the kernels: that is where they differ.
 //
 // Swapped-operand form: S' = K·Q^T puts S'[k][q] in C layout with
 // q = lane&31, so a lane owns ONE query column. The softmax max/sum over
@@ -45,12 +48,13 @@ DEV_INLINE bf16x8 ld8(const short* p) {
 // cvt_pk_asm issues the same instruction from inline asm, which the
 // compiler's hazard tracking does not see. It is safe only where another
 // VALU or permlane instruction sits between it and the MFMA that reads
-// the result, as the permlane32_swap of pv_tile and of dq v3 does. With
-// its result as the A operand of the very next MFMA, dq v5's dQ came out
-// wrong in the 32 columns of that first MFMA (measured; PERFORMANCE.md,
-// backward ladder, "cvt_pk"), which is what a missing VALU-write ->
-// MFMA-read wait state looks like. Moving a kernel from one form to the
-// other changes its code generation: measure it.
+// the result, as the permlane32_swap of pv_tile and of dq v3 does
+// (pack_swap<true>). With its result as the A operand of the very next
+// MFMA, dq v5's dQ came out wrong in the 32 columns of that first MFMA
+// (measured; PERFORMANCE.md, backward ladder, "cvt_pk"), which is what a
+// missing VALU-write -> MFMA-read wait state looks like: dq v5 calls
+// pack_swap<false>. Moving a kernel from one form to the other changes its
+// code generation: measure it.
 DEV_INLINE unsigned int cvt_pk(float lo, float hi) {
   bf16x2 v{(__bf16)lo, (__bf16)hi};
   return __builtin_bit_cast(unsigned int, v);
@@ -61,6 +65,58 @@ DEV_INLINE unsigned int cvt_pk_asm(float lo, float hi) {
   return r;
 }
 
+// Row of C-layout register r; here and below, hi = lane >> 5.
+//
+// A shared function is simplified on its own before it is inlined, so a
+// call is not always the code of the same lines written in place. Where
+// c_row, ld_tr8 or c_store changed a backward kernel's tile loop (the mask
+// compares of every backward kernel, the K gathers of dq v3 and dq v5,
+// dq v3's epilogue, dkv v6's paired reads) the kernel keeps the lines and
+// says so; tools/kernel_isa_diff.py shows what a call site does.
+DEV_INLINE int c_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// Registers 8kc .. 8kc+7 of a C-layout tile (8 of the lane's 16 rows, one
+// column) as the A/B fragment of k-step kc: packed to bf16 and exchanged
+// with the partner lane (guide T12: one permlane32_swap fills two fragment
+// words, no divergent hi/lo branch). ASM chooses the cvt_pk form, see above.
+template <bool ASM>
+DEV_INLINE bf16x8 pack_swap(const f32x16& p, int kc) {
+  auto pk = [](float lo, float hi) {
+    return ASM ? cvt_pk_asm(lo, hi) : cvt_pk(lo, hi);
+  };
+  unsigned int a0 = pk(p[8 * kc + 0], p[8 * kc + 1]);
+  unsigned int a1 = pk(p[8 * kc + 2], p[8 * kc + 3]);
+  unsigned int b0 = pk(p[8 * kc + 4], p[8 * kc + 5]);
+  unsigned int b1 = pk(p[8 * kc + 6], p[8 * kc + 7]);
+  auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+  auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+  u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
+           (unsigned)sw1[1]};
+  return __builtin_bit_cast(bf16x8, pw);
+}
+
+// Two ds_read_tr16_b64 at the LDS addresses p0 and p1 as one fragment:
+// elements 0..3 from p0's 4-row block, 4..7 from p1's.
+DEV_INLINE bf16x8 ld_tr8(const short* p0, const short* p1) {
+  typedef __attribute__((address_space(3))) short4v* lds4;
+  short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4)p0);
+  short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4)p1);
+  short tmp[8] = {lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+  return __builtin_bit_cast(bf16x8, *reinterpret_cast<short8*>(tmp));
+}
+
+// A wave's 32-row x 128-column C-layout tile to bf16 rows at `out`, row
+// stride rs elements.
+DEV_INLINE void c_store(const f32x16 (&acc)[4], short* out, long long rs,
+                        int lane, int hi) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      out[(long long)c_row(r, hi) * rs + 32 * dt + (lane & 31)] =
+          f2bf(acc[dt][r]);
+}
+
 // K LDS XOR-swizzle (guide T2): element column c (a multiple of 8) of
 // row r of a [rows][D] tile sits at column k_swz(r, c), so the S'-phase
 // ds_read_b128 of 32 different rows at one column range spreads over the
@@ -68,8 +124,7 @@ DEV_INLINE unsigned int cvt_pk_asm(float lo, float hi) {
 DEV_INLINE int k_swz(int r, int c) { return c ^ ((r & 7) << 3); }
 
 // S' = K·Q^T for the 32-row sub-tile kt of a swizzled [rows][D] LDS tile;
-// q_frag is the lane's own query row as B fragments. Here and below,
-// hi = lane >> 5.
+// q_frag is the lane's own query row as B fragments.
 template <int D, int ROWS>
 DEV_INLINE f32x16 s_tile(const short (&k_tile)[ROWS][D], int kt, int lane,
                          int hi, const bf16x8 (&q_frag)[D / 16]) {
@@ -114,8 +169,7 @@ DEV_INLINE f32x16 softmax_step(f32x16 s_acc, f32x16 (&o_acc)[DT],
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      int gk = k0s + krow;
+      int gk = k0s + c_row(r, hi);
       bool masked = (gk >= k_lim) || (causal && gk > gq);
       p[r] = masked ? -INFINITY : p[r];
       rmax = fmaxf(rmax, p[r]);
@@ -151,10 +205,9 @@ DEV_INLINE f32x16 softmax_step(f32x16 s_acc, f32x16 (&o_acc)[DT],
 }
 
 // O' += V^T·P for the 32-row sub-tile kt of an unswizzled [rows][D] LDS
-// tile. P -> B fragments by cvt_pk_asm + permlane32_swap (guide T12: one
-// swap fills two fragment words, no divergent hi/lo branch); V^T A
-// fragments by ds_read_tr16_b64 (T10): two reads replace 32 u16 gathers
-// per (16-key chunk, 32-column tile).
+// tile. P -> B fragments by pack_swap; V^T A fragments by ld_tr8 (guide
+// T10): two reads replace 32 u16 gathers per (16-key chunk, 32-column
+// tile).
 template <int D, int ROWS>
 DEV_INLINE void pv_tile(f32x16 p, const short (&v_tile)[ROWS][D], int kt,
                         int lane, int hi, f32x16 (&o_acc)[D / 32]) {
@@ -162,29 +215,12 @@ DEV_INLINE void pv_tile(f32x16 p, const short (&v_tile)[ROWS][D], int kt,
   const int grp16 = (lane >> 4) & 1;
 #pragma unroll
   for (int kc = 0; kc < 2; ++kc) {
-    unsigned int a0 = cvt_pk_asm(p[8 * kc + 0], p[8 * kc + 1]);
-    unsigned int a1 = cvt_pk_asm(p[8 * kc + 2], p[8 * kc + 3]);
-    unsigned int b0 = cvt_pk_asm(p[8 * kc + 4], p[8 * kc + 5]);
-    unsigned int b1 = cvt_pk_asm(p[8 * kc + 6], p[8 * kc + 7]);
-    auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-    auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-    u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
-             (unsigned)sw1[1]};
-    bf16x8 pb = __builtin_bit_cast(bf16x8, pw);
+    bf16x8 pb = pack_swap<true>(p, kc);
     const int vrow0 = 32 * kt + kc * 16 + 8 * hi + (gl >> 2);
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt) {
       const int vcol = dt * 32 + 16 * grp16 + 4 * (gl & 3);
-      auto p0 = (__attribute__((address_space(3))) short4v*)
-          &v_tile[vrow0][vcol];
-      auto p1 = (__attribute__((address_space(3))) short4v*)
-          &v_tile[vrow0 + 4][vcol];
-      short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p0);
-      short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p1);
-      short vtmp[8] = {lo[0], lo[1], lo[2], lo[3],
-                       hi4[0], hi4[1], hi4[2], hi4[3]};
-      bf16x8 va =
-          __builtin_bit_cast(bf16x8, *reinterpret_cast<short8*>(vtmp));
+      bf16x8 va = ld_tr8(&v_tile[vrow0][vcol], &v_tile[vrow0 + 4][vcol]);
       o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb, o_acc[dt],
                                                           0, 0, 0);
     }
@@ -266,8 +302,7 @@ DEV_INLINE void softmax_pack(f32x16 s_acc, float& m_run, float& l_run,
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      int gk = k0s + krow;
+      int gk = k0s + c_row(r, hi);
       bool masked = (gk >= k_lim) || (causal && gk > gq);
       p[r] = masked ? -INFINITY : p[r];
       rmax = fmaxf(rmax, p[r]);
@@ -303,17 +338,7 @@ DEV_INLINE void softmax_pack(f32x16 s_acc, float& m_run, float& l_run,
   need = need_rescale;
   sc_out = sc;
 #pragma unroll
-  for (int kc = 0; kc < 2; ++kc) {
-    unsigned int a0 = cvt_pk_asm(p[8 * kc + 0], p[8 * kc + 1]);
-    unsigned int a1 = cvt_pk_asm(p[8 * kc + 2], p[8 * kc + 3]);
-    unsigned int b0 = cvt_pk_asm(p[8 * kc + 4], p[8 * kc + 5]);
-    unsigned int b1 = cvt_pk_asm(p[8 * kc + 6], p[8 * kc + 7]);
-    auto sw0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-    auto sw1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-    u32x4 pw{(unsigned)sw0[0], (unsigned)sw1[0], (unsigned)sw0[1],
-             (unsigned)sw1[1]};
-    pb[kc] = __builtin_bit_cast(bf16x8, pw);
-  }
+  for (int kc = 0; kc < 2; ++kc) pb[kc] = pack_swap<true>(p, kc);
 }
 
 // O' *= sc on the lanes whose running max moved (softmax_step's tail).
@@ -335,14 +360,7 @@ DEV_INLINE void pv_sub(const bf16x8 (&pb)[2], const short* v_img, int tb0,
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       const int o = 2048 * kc + 256 * dt;
-      short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) short4v*)(v_img + tb0 + o));
-      short4v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) short4v*)(v_img + tb1 + o));
-      short vtmp[8] = {lo[0], lo[1], lo[2], lo[3],
-                       hi4[0], hi4[1], hi4[2], hi4[3]};
-      bf16x8 va =
-          __builtin_bit_cast(bf16x8, *reinterpret_cast<short8*>(vtmp));
+      bf16x8 va = ld_tr8(v_img + tb0 + o, v_img + tb1 + o);
       o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb[kc],
                                                           o_acc[dt], 0, 0, 0);
     }

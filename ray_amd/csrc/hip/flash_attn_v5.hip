@@ -140,7 +140,7 @@ extern "C" __global__ __launch_bounds__(256) void flash_attn_fwd_v5_bf16(
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        int d = (r & 3) + 8 * (r >> 2) + 4 * hi + 32 * t;
+        int d = c_row(r, hi) + 32 * t;
         op[d] = f2bf(o_acc[t][r] * inv);
       }
   }

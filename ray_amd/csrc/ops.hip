@@ -11,7 +11,8 @@
 // Flash attention has two paths, chosen from the shape alone:
 //   T % 256 == 0: 256-row kernels (fwd v7, dq v5, dkv v6), which read
 //                 contiguous BHTD or BTHD-view tensors;
-//   otherwise:    128-row kernels (fwd v5, dq/dv/dk v3), contiguous BHTD.
+//   otherwise:    128-row kernels (fwd v5, dq v3, the two instances of dkv
+//                 v3), contiguous BHTD.
 // Each file below compiles on its own.
 #include "hip/flash_attn_v5.hip"
 #include "hip/flash_attn_v7.hip"
@@ -32,6 +33,10 @@ static inline hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
+static inline bool aligned16(const at::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
 static inline int grid_for(long long n, int block = 256, int cap = 2048) {
   long long g = (n + block - 1) / block;
   return (int)std::min<long long>(g, cap);
@@ -45,8 +50,7 @@ static inline int grid_for(long long n, int block = 256, int cap = 2048) {
   CHECK_IN(t);                                                          \
   TORCH_CHECK(t.scalar_type() == at::kBFloat16,                         \
               "rmsnorm: " #t " must be bf16, got ", t.scalar_type());   \
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,      \
-              "rmsnorm: " #t " must be 16-byte aligned")
+  TORCH_CHECK(aligned16(t), "rmsnorm: " #t " must be 16-byte aligned")
 
 static int rmsnorm_check_hw(const at::Tensor& x, const at::Tensor& w) {
   TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "rmsnorm: x must be [..., H]");
@@ -256,9 +260,6 @@ at::Tensor rope_apply(at::Tensor x, at::Tensor cosT, at::Tensor sinT,
                ? at::empty_like(x)
                : at::empty({x.size(0), x.size(1), x.size(2), x.size(3)},
                            x.options());
-  auto aligned16 = [](const at::Tensor& t) {
-    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
-  };
   // eight pairs per lane with 16-byte accesses where the layout allows it
   const bool vec = D % 16 == 0 && in_rs % 8 == 0 && aligned16(x) &&
                    aligned16(y) && aligned16(cosT) && aligned16(sinT);
@@ -336,6 +337,28 @@ static bool check_paged_cache(const at::Tensor& k_cache,
   return fp8;
 }
 
+// What decode and prefill attention check alike: the head dimension, the
+// caches (check_paged_cache, whose result is returned), the GQA ratio the
+// kernels are instantiated for and the block table. *Hkv is the caches'.
+static bool check_paged_attn(const at::Tensor& k_cache,
+                             const at::Tensor& v_cache,
+                             const at::Tensor& block_table, int B, int Hq,
+                             int D, double k_scale, double v_scale, int* Hkv) {
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
+  *Hkv = (int)k_cache.size(1);
+  const bool fp8 = check_paged_cache(k_cache, v_cache, *Hkv, D, k_scale,
+                                     v_scale);
+  TORCH_CHECK(*Hkv >= 1 && Hq % *Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const int rep = Hq / *Hkv;
+  TORCH_CHECK(rep == 1 || rep == 2 || rep == 4 || rep == 8,
+              "paged_attn: Hq/Hkv must be 1, 2, 4 or 8");
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+              block_table.size(1) >= 1,
+              "block_table must be [B, max_pages]");
+  return fp8;
+}
+
 static void launch_paged_reduce(const at::Tensor& ws, at::Tensor& out, int B,
                                 int Hq, int D, int S) {
   const float* ws_o = ws.data_ptr<float>();
@@ -390,18 +413,10 @@ at::Tensor paged_attn_decode(at::Tensor q, at::Tensor k_cache,
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
   TORCH_CHECK(q.dim() == 3, "q must be [B, Hq, D]");
   int B = (int)q.size(0), Hq = (int)q.size(1), D = (int)q.size(2);
-  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
-  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
-  int Hkv = (int)k_cache.size(1);
-  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
-                                     v_scale);
-  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  int Hkv;
+  const bool fp8 = check_paged_attn(k_cache, v_cache, block_table, B, Hq, D,
+                                    k_scale, v_scale, &Hkv);
   int rep = Hq / Hkv;
-  TORCH_CHECK(rep == 1 || rep == 2 || rep == 4 || rep == 8,
-              "paged_attn: Hq/Hkv must be 1, 2, 4 or 8");
-  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
-              block_table.size(1) >= 1,
-              "block_table must be [B, max_pages]");
   TORCH_CHECK(seq_lens.dim() == 1 && seq_lens.size(0) == B,
               "seq_lens must be [B]");
   TORCH_CHECK(B >= 1 && B <= 65535 && Hkv <= 65535,
@@ -461,25 +476,13 @@ at::Tensor paged_attn_prefill(at::Tensor q, at::Tensor k_cache,
   CHECK_I32(q_lens);
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
   TORCH_CHECK(q.dim() == 4, "q must be [B, Tq, Hq, D]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "paged_attn_prefill: q must be 16-byte aligned");
+  TORCH_CHECK(aligned16(q), "paged_attn_prefill: q must be 16-byte aligned");
   int B = (int)q.size(0), Hq = (int)q.size(2), D = (int)q.size(3);
-  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
-  TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [num_pages, Hkv, 16, D]");
-  int Hkv = (int)k_cache.size(1);
-  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
-                                     v_scale);
-  TORCH_CHECK(fp8 ||
-              (reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
-               reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0),
+  int Hkv;
+  const bool fp8 = check_paged_attn(k_cache, v_cache, block_table, B, Hq, D,
+                                    k_scale, v_scale, &Hkv);
+  TORCH_CHECK(fp8 || (aligned16(k_cache) && aligned16(v_cache)),
               "paged_attn_prefill: caches must be 16-byte aligned");
-  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  int rep = Hq / Hkv;
-  TORCH_CHECK(rep == 1 || rep == 2 || rep == 4 || rep == 8,
-              "paged_attn: Hq/Hkv must be 1, 2, 4 or 8");
-  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
-              block_table.size(1) >= 1,
-              "block_table must be [B, max_pages]");
   TORCH_CHECK(block_table.size(1) <= (1 << 26),
               "paged_attn_prefill: block table too wide");
   TORCH_CHECK(ctx_lens.dim() == 1 && ctx_lens.size(0) == B &&
@@ -528,9 +531,8 @@ static long long paged_row_stride(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
   TORCH_CHECK(t.dim() == 3 && t.stride(2) == 1 && t.stride(1) == t.size(2),
               name, " must be [B, H, D] with a contiguous [H, D] tail");
-  TORCH_CHECK(t.stride(0) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-              name, " rows must be 16-byte aligned");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && aligned16(t), name,
+              " rows must be 16-byte aligned");
   return (long long)t.stride(0);
 }
 
@@ -622,9 +624,8 @@ static long long wgrad_operand(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
   TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1),
               name, " must be 2-D with unit column stride");
-  TORCH_CHECK(t.stride(0) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-              name, " rows must be 16-byte aligned");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && aligned16(t), name,
+              " rows must be 16-byte aligned");
   TORCH_CHECK(t.size(1) % 256 == 0 && t.size(1) >= 256, name,
               ": columns must be a multiple of 256");
   return (long long)t.stride(0);
@@ -782,8 +783,7 @@ static void ce_check(const at::Tensor& logits, const at::Tensor& target) {
               "ce: target must be [N]");
   // the kernels use 16-byte loads only when V % 8 == 0; then every row
   // is aligned exactly when the base is
-  TORCH_CHECK(logits.size(1) % 8 != 0 ||
-              reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+  TORCH_CHECK(logits.size(1) % 8 != 0 || aligned16(logits),
               "ce: logits must be 16-byte aligned");
 }
 
@@ -837,8 +837,8 @@ static inline int attn_layout(const at::Tensor& t, long long* rs) {
   if (t.stride(1) != D || t.stride(0) != T * r || r < H * D) return -1;
   *rs = r;
   if (r == H * D) return 1;
-  if (r % 8 == 0 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
-      T * r < (1ll << 31) && 64 * r < (1ll << 30))
+  if (r % 8 == 0 && aligned16(t) && T * r < (1ll << 31) &&
+      64 * r < (1ll << 30))
     return 1;
   return -1;
 }
@@ -939,9 +939,8 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
                 "dqkv must be bf16 [B, T, (Hq+2Hkv)*D] on the GPU");
     const long long r = g.stride(1);
     TORCH_CHECK(g.stride(2) == 1 && g.stride(0) == T * r && r >= W &&
-                    r % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0 &&
-                    T * r < (1ll << 31) && 64 * r < (1ll << 30),
+                    r % 8 == 0 && aligned16(g) && T * r < (1ll << 31) &&
+                    64 * r < (1ll << 30),
                 "dqkv rows must be 16-byte aligned, at stride >= "
                 "(Hq+2Hkv)*D with T * stride < 2^31");
     auto section = [&](long long col, int H) {
@@ -1000,16 +999,17 @@ std::vector<at::Tensor> flash_attn_bwd(at::Tensor q, at::Tensor k,
   } else {
     // 128-row blocks, contiguous BHTD only (checked above): K/V
     // register-resident, 64-row double-buffered q/dO tiles; dV and dK are
-    // separate kernels so that each fits 2 waves/SIMD.
+    // two instances of fa_bwd_dkv_v3_bf16 so that each fits 2 waves/SIMD.
     const dim3 blk(256);
     hipLaunchKernelGGL(fa_bwd_dq_v3_bf16, dim3(T / 128, B * Hq), blk, 0, st,
                        qp, kp, vp, dop, lsep, dsp, dqp, B, Hq, Hkv, T, c,
                        scale, /*bthd=*/0);
-    hipLaunchKernelGGL(fa_bwd_dv_v3_bf16, dim3(T / 128, B * Hkv), blk, 0, st,
-                       qp, kp, vp, dop, lsep, dvp, B, Hq, Hkv, T, c, scale);
-    hipLaunchKernelGGL(fa_bwd_dk_v3_bf16, dim3(T / 128, B * Hkv), blk, 0, st,
-                       qp, kp, vp, dop, lsep, dsp, dkp, B, Hq, Hkv, T, c,
-                       scale);
+    hipLaunchKernelGGL(fa_bwd_dkv_v3_bf16<false>, dim3(T / 128, B * Hkv), blk,
+                       0, st, qp, kp, vp, dop, lsep, dsp, dvp, B, Hq, Hkv, T,
+                       c, scale);
+    hipLaunchKernelGGL(fa_bwd_dkv_v3_bf16<true>, dim3(T / 128, B * Hkv), blk,
+                       0, st, qp, kp, vp, dop, lsep, dsp, dkp, B, Hq, Hkv, T,
+                       c, scale);
   }
   return {dq, dk, dv};
 }
@@ -1032,16 +1032,14 @@ void rope_qk_inplace(at::Tensor qkv, at::Tensor cosT, at::Tensor sinT,
   TORCH_CHECK(D > 0 && D % 16 == 0, "rope_qk_inplace: D must be a multiple "
                                     "of 16");
   TORCH_CHECK(qkv.stride(2) == 1 && rs >= W && rs % 8 == 0 &&
-                  (B == 1 || qkv.stride(0) == T * rs) &&
-                  reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+                  (B == 1 || qkv.stride(0) == T * rs) && aligned16(qkv),
               "rope_qk_inplace: rows must be 16-byte aligned with a uniform "
               "stride >= W");
   TORCH_CHECK(cosT.scalar_type() == at::kFloat &&
                   sinT.scalar_type() == at::kFloat && cosT.dim() == 2 &&
                   cosT.size(0) >= T && cosT.size(1) == D / 2 &&
-                  sinT.sizes() == cosT.sizes() &&
-                  reinterpret_cast<uintptr_t>(cosT.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(sinT.data_ptr()) % 16 == 0,
+                  sinT.sizes() == cosT.sizes() && aligned16(cosT) &&
+                  aligned16(sinT),
               "rope_qk_inplace: cosT/sinT must be 16-byte-aligned fp32 "
               "[>= T, D/2]");
   const int n_rot = (int)(n_heads + n_kv_heads);

@@ -43,10 +43,15 @@ OLD_REL_ERR = {
 # The 128-row path (T % 256 != 0) at three key and three query blocks:
 # diagonal and off-diagonal tiles, GQA rep 4 and a batch stride; run from
 # contiguous BHTD tensors and from BTHD views, which are copied at this T.
+# The last shape is the smallest at which the dK/dV kernel's staging and
+# causal skip can go wrong: one key block, and per head a q-tile sequence of
+# two tiles, so the flattened loop crosses a head boundary at every second
+# tile.
 SHAPES_128 = [
     (2, 8, 2, 384, False, True),
     (2, 8, 2, 384, True, True),
     (1, 4, 4, 384, False, False),
+    (1, 4, 2, 128, False, True),
 ]
 
 

@@ -6,7 +6,8 @@ ray_amd/_hip_ops.so, loaded side by side in one process:
 Same bits: dq, dk and dv of the two builds must be torch.equal at the shapes
 of tests/test_fa_bwd_dq_order.py and of tests/test_fa_bwd_v6.py and at
 B2 Hq32 Hkv8 T4096, each on contiguous [B,H,T,D] tensors, on BTHD views and
-on the column sections of a packed buffer with the packed gradient. Timing:
+on the column sections of a packed buffer with the packed gradient, and at
+three shapes of the 128-row path on contiguous tensors. Timing:
 the backward unit (the binding launches fa_bwd_prep, the dq and the dkv
 kernel together), the two builds alternating, median [min, max]
 microseconds per call over 2 x 7 repetitions of 20 calls (device events);
@@ -34,6 +35,8 @@ BIT_SHAPES = [
     # tests/test_fa_bwd_v6.py (its T256 and T512 shapes are above)
     (2, 8, 2, 768, True), (2, 4, 1, 1024, True),
     (2, 32, 8, 4096, True),
+    # the 128-row kernels (T % 256 != 0): contiguous [B,H,T,D] only
+    (2, 8, 2, 384, True), (1, 4, 4, 384, False), (1, 4, 2, 128, True),
 ]
 
 # (B, Hq, Hkv, T, layout), causal
@@ -41,6 +44,7 @@ TIME_SHAPES = [
     (8, 32, 8, 4096, "bhtd"), (8, 32, 8, 4096, "view"),
     (8, 32, 8, 4096, "packed"), (16, 32, 8, 2048, "bhtd"),
     (2, 32, 8, 8192, "bhtd"), (8, 32, 32, 4096, "bhtd"),
+    (8, 32, 8, 3968, "bhtd"),  # the 128-row kernels
 ]
 
 
@@ -72,7 +76,8 @@ def same_bits(K, P, ops):
     bad = 0
     torch.manual_seed(11)
     for B, Hq, Hkv, T, causal in BIT_SHAPES:
-        for layout in ("bhtd", "view", "packed"):
+        for layout in ("bhtd", "view", "packed") if T % 256 == 0 \
+                else ("bhtd",):
             (q, k, v, g), buf = _operands(ops, B, Hq, Hkv, T, layout)
             out, lse = K.flash_attn_fwd(q, k, v, causal, 0, True)
             res = []
