@@ -21,6 +21,7 @@
 #include "hip/fa_bwd_dq_v5.hip"
 #include "hip/fa_bwd_dkv_v6.hip"
 #include "hip/gemv.hip"
+#include "hip/linear_w8.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
@@ -294,6 +295,55 @@ at::Tensor gemv(at::Tensor x, at::Tensor w) {
   hipLaunchKernelGGL(gemv_bf16, dim3(blocks), dim3(256), 0, cur_stream(),
                      (const short*)w.data_ptr(), (const short*)x.data_ptr(),
                      (short*)y.data_ptr(), N, B, K);
+  return y;
+}
+
+// ---------------- FP8 weight-only skinny GEMM (decode linear) ----------------
+
+// y[M,N] = x[M,K] · (wq[N,K] * scale[N])^T; x bf16, wq float8_e4m3fn, scale
+// fp32. `tile` picks the channels per block (16 or 32; 0: by shape) and is
+// there for tools/linear_w8_bench.py; the result does not depend on it.
+at::Tensor linear_w8(at::Tensor x, at::Tensor wq, at::Tensor scale,
+                     int64_t tile) {
+  CHECK_IN(x); CHECK_IN(wq); CHECK_IN(scale);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "linear_w8: x must be bf16");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn,
+              "linear_w8: wq must be float8_e4m3fn, got ", wq.scalar_type());
+  TORCH_CHECK(scale.scalar_type() == at::kFloat,
+              "linear_w8: scale must be fp32");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2,
+              "linear_w8: x must be [M, K] and wq [N, K]");
+  const long long M = x.size(0), K = x.size(1), N = wq.size(0);
+  TORCH_CHECK(M >= 1 && M <= 32, "linear_w8: rows must be 1..32");
+  TORCH_CHECK(wq.size(1) == K && K >= 128 && K % 128 == 0 &&
+              K < (1ll << 31), "linear_w8: K must be a multiple of 128");
+  TORCH_CHECK(N >= 1 && N < (1ll << 31) - 32, "linear_w8: bad N");
+  TORCH_CHECK(scale.numel() == N, "linear_w8: scale must have N elements");
+  TORCH_CHECK(aligned16(x) && aligned16(wq),
+              "linear_w8: x and wq must be 16-byte aligned");
+  TORCH_CHECK(tile == 0 || tile == 16 || tile == 32,
+              "linear_w8: tile must be 0, 16 or 32");
+  // 32 channels per block halve the L2 traffic for x. Measured with
+  // tools/linear_w8_bench.py --tiles 16,32 (PERFORMANCE.md): they win at
+  // N = 128256 for every M and at N = 6144 and 14336 for M = 8 and 32; at
+  // N = 4096 they leave half the CUs without a block and lose.
+  const int nt = tile ? (int)tile / 16
+                      : (N >= 16384 || (N >= 6144 && M > 4) ? 2 : 1);
+  auto y = at::empty({M, N}, x.options());
+  const unsigned blocks = (unsigned)((N + 16 * nt - 1) / (16 * nt));
+#define W8_LAUNCH(MT, NT)                                                   \
+  hipLaunchKernelGGL((linear_w8_bf16_kernel<MT, NT>), dim3(blocks),         \
+                     dim3(64 * W8_WAVES), 0, cur_stream(),                  \
+                     (const short*)x.data_ptr(),                            \
+                     (const unsigned char*)wq.data_ptr(),                   \
+                     scale.data_ptr<float>(), (short*)y.data_ptr(), (int)M, \
+                     (int)N, (int)K)
+  if (M <= 16) {
+    if (nt == 1) { W8_LAUNCH(1, 1); } else { W8_LAUNCH(1, 2); }
+  } else {
+    if (nt == 1) { W8_LAUNCH(2, 1); } else { W8_LAUNCH(2, 2); }
+  }
+#undef W8_LAUNCH
   return y;
 }
 
@@ -1059,6 +1109,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_qk_inplace", &rope_qk_inplace);
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("gemv", &gemv);
+  m.def("linear_w8", &linear_w8, py::arg("x"), py::arg("wq"), py::arg("scale"),
+        py::arg("tile") = 0);
   m.def("gemm_wgrad", &gemm_wgrad, py::arg("dy"), py::arg("x"),
         py::arg("out") = py::none());
   m.def("gemm_wgrad_grouped", &gemm_wgrad_grouped);

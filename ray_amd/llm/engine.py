@@ -19,6 +19,7 @@ from ray_amd.models.llama import (
     GraphedDecoder,
     KVCache,
     LlamaModel,
+    quantize_linears_fp8,
 )
 
 
@@ -48,6 +49,12 @@ class LLMConfig:
     kv_cache_dtype: str = "auto"
     kv_k_scale: float = 1.0
     kv_v_scale: float = 1.0
+    # ContinuousBatchingEngine with kv_cache="paged" only. weight_dtype:
+    # "auto" or "bf16" (the model dtype) or "fp8" ("fp8_e4m3" is the same):
+    # every projection and lm_head hold one byte per weight plus an fp32
+    # scale per output channel (ops.LinearW8), and decode reads them with
+    # the fp8 skinny-GEMM kernel. Activations stay in the model dtype.
+    weight_dtype: str = "auto"
 
 
 # LLMConfig.kv_cache_dtype -> page dtype (None: the model dtype)
@@ -58,10 +65,23 @@ _KV_CACHE_DTYPES = {
     "fp8_e4m3": torch.float8_e4m3fn,
 }
 
+_WEIGHT_DTYPES = ("auto", "bf16", "fp8", "fp8_e4m3")
+
+
+def _fp8_weights(config: LLMConfig) -> bool:
+    if config.weight_dtype not in _WEIGHT_DTYPES:
+        raise ValueError(
+            f"weight_dtype must be one of {sorted(_WEIGHT_DTYPES)}, got "
+            f"{config.weight_dtype!r}")
+    return config.weight_dtype.startswith("fp8")
+
 
 class LLMEngine:
     def __init__(self, config: LLMConfig):
         self.config = config
+        if _fp8_weights(config):
+            raise ValueError("weight_dtype='fp8' needs "
+                             "ContinuousBatchingEngine with kv_cache='paged'")
         cfg = CONFIGS[config.model_id]
         self.model_cfg = cfg
         self.device = (
@@ -205,6 +225,10 @@ class ContinuousBatchingEngine:
         kv_dtype = _KV_CACHE_DTYPES[config.kv_cache_dtype]
         if kv_dtype == torch.float8_e4m3fn and not self._paged:
             raise ValueError("kv_cache_dtype='fp8' needs kv_cache='paged'")
+        if _fp8_weights(config):
+            if not self._paged:
+                raise ValueError("weight_dtype='fp8' needs kv_cache='paged'")
+            quantize_linears_fp8(self.model)
         if self._paged:
             from ray_amd.llm.paged import PagedDecoder
 
@@ -233,6 +257,9 @@ class ContinuousBatchingEngine:
                                 device=self.device)
         self.stats = {"requests": 0, "tokens_generated": 0,
                       "decode_steps": 0}
+        self.stats["weight_bytes"] = sum(
+            t.numel() * t.element_size()
+            for t in (*self.model.parameters(), *self.model.buffers()))
         self._sync_page_stats()
 
     def _sync_page_stats(self):

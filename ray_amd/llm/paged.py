@@ -15,6 +15,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ray_amd import ops
+from ray_amd.models.llama import proj
 
 PAGE_SIZE = ops.PAGE_SIZE
 
@@ -456,14 +457,14 @@ class PagedDecoder:
                 q, kp, vp, self.block_table, self.seq_lens,
                 num_splits=self.num_splits, workspace=self.workspace,
                 k_scale=self.pool.k_scale, v_scale=self.pool.v_scale)
-            x = x + lin(attn.reshape(B, 1, -1), at.o_proj.weight)
+            x = x + proj(at.o_proj, attn.reshape(B, 1, -1), lin)
             hm = layer.mlp_norm(x)
             mp = layer.mlp
-            x = x + lin(ops.swiglu(lin(hm, mp.gate_proj.weight),
-                                   lin(hm, mp.up_proj.weight)),
-                        mp.down_proj.weight)
+            x = x + proj(mp.down_proj,
+                         ops.swiglu(proj(mp.gate_proj, hm, lin),
+                                    proj(mp.up_proj, hm, lin)), lin)
         x = m.final_norm(x)
-        return lin(x, m.lm_head.weight)[:, 0]
+        return proj(m.lm_head, x, lin)[:, 0]
 
     @torch.no_grad()  # grad mode gates the GEMV fast path (linear_sb)
     def capture(self):

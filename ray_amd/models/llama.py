@@ -50,6 +50,35 @@ CONFIGS = {
 }
 
 
+def proj(mod, x, lin=None):
+    """The projection `mod` applied to x. `lin(x, weight)` overrides the
+    matmul of a bf16 Linear (decode paths pass the GEMV fast path); an
+    ops.LinearW8 always runs its own fp8-weight linear."""
+    if lin is None or isinstance(mod, ops.LinearW8):
+        return mod(x)
+    return lin(x, mod.weight)
+
+
+def quantize_linears_fp8(model: "LlamaModel") -> "LlamaModel":
+    """Replace, in place, every decoder-layer projection and lm_head by an
+    ops.LinearW8 (fp8 e4m3 weights, one fp32 scale per output channel).
+    The embedding and the norms keep the model dtype; a tied lm_head is
+    quantised from the embedding's values and no longer shares them. The
+    model then serves inference only, through PagedDecoder or its own
+    forward."""
+    def swap(parent, names):
+        for name in names:
+            if hasattr(parent, name):
+                setattr(parent, name,
+                        ops.LinearW8.from_linear(getattr(parent, name)))
+
+    for layer in model.layers:
+        swap(layer.attn, ("qkv_proj", "q_proj", "k_proj", "v_proj", "o_proj"))
+        swap(layer.mlp, ("gate_proj", "up_proj", "down_proj"))
+    swap(model, ("lm_head",))
+    return model
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: LlamaConfig, dtype=torch.bfloat16):
         super().__init__()
@@ -86,21 +115,16 @@ class Attention(nn.Module):
         cfg = self.cfg
         hd = self.head_dim
         if self._fused_qkv:
-            qkv = (self.qkv_proj(x) if lin is None
-                   else lin(x, self.qkv_proj.weight))
+            qkv = proj(self.qkv_proj, x, lin)
             q, k, v = qkv.split(
                 [cfg.num_heads * hd, cfg.num_kv_heads * hd,
                  cfg.num_kv_heads * hd], dim=-1)
             return (q.view(B, T, cfg.num_heads, hd),
                     k.view(B, T, cfg.num_kv_heads, hd),
                     v.view(B, T, cfg.num_kv_heads, hd))
-        if lin is None:
-            return (self.q_proj(x).view(B, T, cfg.num_heads, hd),
-                    self.k_proj(x).view(B, T, cfg.num_kv_heads, hd),
-                    self.v_proj(x).view(B, T, cfg.num_kv_heads, hd))
-        return (lin(x, self.q_proj.weight).view(B, T, cfg.num_heads, hd),
-                lin(x, self.k_proj.weight).view(B, T, cfg.num_kv_heads, hd),
-                lin(x, self.v_proj.weight).view(B, T, cfg.num_kv_heads, hd))
+        return (proj(self.q_proj, x, lin).view(B, T, cfg.num_heads, hd),
+                proj(self.k_proj, x, lin).view(B, T, cfg.num_kv_heads, hd),
+                proj(self.v_proj, x, lin).view(B, T, cfg.num_kv_heads, hd))
 
     def forward(self, x, cosT, sinT, kv_cache=None, pos0: int = 0):
         B, T, H = x.shape
@@ -117,6 +141,7 @@ class Attention(nn.Module):
 
         if (flash(x) and self._fused_qkv and T % 256 == 0 and pos0 == 0
                 and ops._FUSED_QKV_ATTN
+                and not isinstance(self.qkv_proj, ops.LinearW8)
                 and self.qkv_proj.weight.dtype == torch.bfloat16):
             # RoPE in place on the projection output, attention on its
             # q/k/v column sections, one packed gradient in backward
@@ -162,6 +187,9 @@ class MLP(nn.Module):
         )
 
     def forward(self, x):
+        if isinstance(self.gate_proj, ops.LinearW8):
+            return self.down_proj(
+                ops.swiglu(self.gate_proj(x), self.up_proj(x)))
         gate, up = ops.swiglu_mlp_in(
             x, self.gate_proj.weight, self.up_proj.weight)
         return self.down_proj(ops.swiglu(gate, up))
@@ -332,15 +360,15 @@ class GraphedDecoder:
                 attn_mask=self.mask.to(q.dtype),
                 enable_gqa=True,
             )
-            x = x + lin(attn.permute(0, 2, 1, 3).reshape(B, 1, -1),
-                        at.o_proj.weight)
+            x = x + proj(at.o_proj,
+                         attn.permute(0, 2, 1, 3).reshape(B, 1, -1), lin)
             hm = layer.mlp_norm(x)
             mp = layer.mlp
-            x = x + lin(ops.swiglu(lin(hm, mp.gate_proj.weight),
-                                   lin(hm, mp.up_proj.weight)),
-                        mp.down_proj.weight)
+            x = x + proj(mp.down_proj,
+                         ops.swiglu(proj(mp.gate_proj, hm, lin),
+                                    proj(mp.up_proj, hm, lin)), lin)
         x = m.final_norm(x)
-        return lin(x, m.lm_head.weight)[:, 0]
+        return proj(m.lm_head, x, lin)[:, 0]
 
     @torch.no_grad()  # grad mode gates the GEMV fast path (linear_sb)
     def capture(self):
@@ -450,15 +478,15 @@ class BatchedDecoder:
                 attn_mask=self.mask.to(q.dtype),
                 enable_gqa=True,
             )
-            x = x + lin(attn.permute(0, 2, 1, 3).reshape(B, 1, -1),
-                        at.o_proj.weight)
+            x = x + proj(at.o_proj,
+                         attn.permute(0, 2, 1, 3).reshape(B, 1, -1), lin)
             hm = layer.mlp_norm(x)
             mp = layer.mlp
-            x = x + lin(ops.swiglu(lin(hm, mp.gate_proj.weight),
-                                   lin(hm, mp.up_proj.weight)),
-                        mp.down_proj.weight)
+            x = x + proj(mp.down_proj,
+                         ops.swiglu(proj(mp.gate_proj, hm, lin),
+                                    proj(mp.up_proj, hm, lin)), lin)
         x = m.final_norm(x)
-        return lin(x, m.lm_head.weight)[:, 0]
+        return proj(m.lm_head, x, lin)[:, 0]
 
 
 class _SlotCacheView:

@@ -230,6 +230,74 @@ def linear_sb(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------
+# FP8 weight-only linear for decode (csrc/hip/linear_w8.hip)
+# --------------------------------------------------------------------------
+
+def quantize_weight_fp8(w: torch.Tensor):
+    """[N, K] finite weights -> (wq float8_e4m3fn [N, K], scale fp32 [N]).
+    Per output channel scale = amax(|w[n, :]|) / 448 (1 for a row of
+    zeros) and wq = e4m3fn_rne(clamp(fp32(w) / scale, -448, 448)): the
+    saturating rule of quantize_kv_fp8 with a per-row scale, so no byte
+    is a NaN. The weight dequantises as wq.float() * scale[:, None]."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    wq = (wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX)
+    return wq.to(torch.float8_e4m3fn), scale
+
+
+def linear_w8_ref(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor):
+    """fp64 reference of linear_w8, returned as fp32."""
+    w = wq.float().double() * scale.double()[:, None]
+    return (x.double() @ w.t()).float()
+
+
+def linear_w8(x: torch.Tensor, wq: torch.Tensor,
+              scale: torch.Tensor) -> torch.Tensor:
+    """x[..., K] · (wq[N, K] * scale[N])^T with fp8 weights (see
+    quantize_weight_fp8). bf16 GPU activations of at most 32 rows with
+    K % 128 == 0 and grad off run the skinny-GEMM kernel, which reads one
+    byte per weight. Everything else (CPU, prefill chunks, odd shapes, grad
+    on) dequantises the weight to the activation dtype and calls F.linear:
+    there is no fp8 prefill GEMM, prefill pays a dequantisation per
+    call."""
+    K = x.shape[-1]
+    rows = x.numel() // K
+    if x.is_cuda:
+        _require_ext("linear_w8")
+        if (x.dtype == torch.bfloat16 and 1 <= rows <= 32 and K % 128 == 0
+                and not torch.is_grad_enabled() and wq.is_contiguous()
+                and wq.data_ptr() % 16 == 0):
+            x2 = x.reshape(rows, K).contiguous()
+            if x2.data_ptr() % 16 == 0:
+                y = _K.linear_w8(x2, wq, scale.contiguous())
+                return y.view(*x.shape[:-1], wq.shape[0])
+    w = (wq.float() * scale[:, None]).to(x.dtype)
+    return torch.nn.functional.linear(x, w)
+
+
+class LinearW8(torch.nn.Module):
+    """A bias-free linear whose weight is stored as fp8 bytes plus one fp32
+    scale per output channel (buffers `wq`, `scale`); it holds no bf16
+    copy of the weight."""
+
+    def __init__(self, wq: torch.Tensor, scale: torch.Tensor):
+        super().__init__()
+        self.out_features, self.in_features = wq.shape
+        self.register_buffer("wq", wq)
+        self.register_buffer("scale", scale)
+
+    @classmethod
+    def from_linear(cls, linear: torch.nn.Linear) -> "LinearW8":
+        if linear.bias is not None:
+            raise ValueError("LinearW8 has no bias")
+        return cls(*quantize_weight_fp8(linear.weight))
+
+    def forward(self, x):
+        return linear_w8(x, self.wq, self.scale)
+
+
+# --------------------------------------------------------------------------
 # Linear with a hand-written weight-gradient GEMM (csrc/hip/gemm_wgrad.hip)
 # --------------------------------------------------------------------------
 

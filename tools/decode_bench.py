@@ -4,11 +4,14 @@
     python tools/decode_bench.py [--model llama3-8b] [--tokens 128]
                                  [--ctx N[,N...]] [--paged] [--reps R]
                                  [--kv-dtype bf16,fp8]
+                                 [--weight-dtype bf16|fp8]
 
 --ctx N starts decoding at context length N (default 64, i.e. tokens
 64..72+tokens); --paged adds a row per batch for the graph-captured
 PagedDecoder (paged KV cache + fused decode attention) at the same
 positions, once per --kv-dtype (fp8: one-byte OCP e4m3fn pages).
+--weight-dtype fp8 quantises the model's projections and lm_head to fp8
+(quantize_linears_fp8) before any decoder is built.
 """
 import argparse
 import os
@@ -19,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from ray_amd.models.llama import CONFIGS, GraphedDecoder, LlamaModel
+from ray_amd.models.llama import (CONFIGS, GraphedDecoder, LlamaModel,
+                                  quantize_linears_fp8)
 
 
 def bench(dec, cfg, B, n_tokens, prefill=64):
@@ -74,6 +78,8 @@ def main():
                          "shows the median and [min, max] ms/step")
     ap.add_argument("--kv-dtype", default="bf16",
                     help="--paged cache formats, comma-separated: bf16, fp8")
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: one-byte weights, per-channel scales")
     args = ap.parse_args()
     kv_dtypes = args.kv_dtype.split(",")
     assert set(kv_dtypes) <= {"bf16", "fp8"}, kv_dtypes
@@ -84,6 +90,9 @@ def main():
     model = LlamaModel(cfg, dtype=torch.bfloat16).to(dev).eval()
     model.cosT = model.cosT.to(dev)
     model.sinT = model.sinT.to(dev)
+    if args.weight_dtype == "fp8":
+        quantize_linears_fp8(model)
+        print("# weights fp8 (e4m3, per-channel scales)")
 
     def timed(fn):
         ms = sorted(fn() / args.tokens * 1e3 for _ in range(args.reps))
