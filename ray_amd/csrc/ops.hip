@@ -22,6 +22,7 @@
 #include "hip/fa_bwd_dkv_v6.hip"
 #include "hip/gemv.hip"
 #include "hip/linear_w8.hip"
+#include "hip/linear_w8_gemm.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
@@ -344,6 +345,78 @@ at::Tensor linear_w8(at::Tensor x, at::Tensor wq, at::Tensor scale,
     if (nt == 1) { W8_LAUNCH(2, 1); } else { W8_LAUNCH(2, 2); }
   }
 #undef W8_LAUNCH
+  return y;
+}
+
+// ---------------- FP8 weight-only GEMM (33+ rows) ----------------
+
+// The same product as linear_w8 for any number of rows, N % 128 == 0
+// (csrc/hip/linear_w8_gemm.hip). split: slices of K (0: the rule below);
+// rows_tile: 64 or 128 rows per block (0: 64 up to 64 rows, else 128). The
+// overrides are there for tools/linear_w8_bench.py and the tests. The result
+// depends on the split (the order of the fp32 sums), not on rows_tile.
+at::Tensor linear_w8_gemm(at::Tensor x, at::Tensor wq, at::Tensor scale,
+                          int64_t split, int64_t rows_tile) {
+  CHECK_IN(x); CHECK_IN(wq); CHECK_IN(scale);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16,
+              "linear_w8_gemm: x must be bf16");
+  TORCH_CHECK(wq.scalar_type() == at::kFloat8_e4m3fn,
+              "linear_w8_gemm: wq must be float8_e4m3fn, got ",
+              wq.scalar_type());
+  TORCH_CHECK(scale.scalar_type() == at::kFloat,
+              "linear_w8_gemm: scale must be fp32");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2,
+              "linear_w8_gemm: x must be [M, K] and wq [N, K]");
+  const long long M = x.size(0), K = x.size(1), N = wq.size(0);
+  TORCH_CHECK(M >= 1 && M < (1ll << 22), "linear_w8_gemm: bad row count");
+  TORCH_CHECK(wq.size(1) == K && K >= 128 && K % 128 == 0 &&
+              K < (1ll << 31), "linear_w8_gemm: K must be a multiple of 128");
+  TORCH_CHECK(N >= 128 && N % 128 == 0 && N < (1ll << 31),
+              "linear_w8_gemm: N must be a multiple of 128");
+  TORCH_CHECK(scale.numel() == N,
+              "linear_w8_gemm: scale must have N elements");
+  TORCH_CHECK(aligned16(x) && aligned16(wq),
+              "linear_w8_gemm: x and wq must be 16-byte aligned");
+  TORCH_CHECK(rows_tile == 0 || rows_tile == 64 || rows_tile == 128,
+              "linear_w8_gemm: rows_tile must be 0, 64 or 128");
+  TORCH_CHECK(split >= 0 && split <= 64, "linear_w8_gemm: split must be 0..64");
+  const int bm = rows_tile ? (int)rows_tile : (M <= 64 ? 64 : 128);
+  const long long tiles = (N / 128) * ((M + bm - 1) / bm);
+  const long long steps = K / 64;
+  long long S = split;
+  if (S == 0) {
+    // Two blocks a CU when K allows it, at least 8 steps a slice, and the
+    // fp32 partials (4 bytes written and 4 read per element and slice) no
+    // more than the weight bytes: S*M*N*8 <= N*K.
+    const long long cus =
+        at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    S = std::min({2 * cus / tiles, steps / 8, K / (8 * M), 16ll});
+  }
+  // a slice without steps would only store zeros
+  S = std::max(1ll, std::min(S, steps));
+  auto y = at::empty({M, N}, x.options());
+  at::Tensor ws;
+  if (S > 1) ws = at::empty({S, M, N}, x.options().dtype(at::kFloat));
+  const dim3 grid((unsigned)(N / 128), (unsigned)((M + bm - 1) / bm),
+                  (unsigned)S);
+#define W8G_LAUNCH(BM, SPLIT)                                                \
+  hipLaunchKernelGGL((linear_w8_gemm_kernel<BM, SPLIT>), grid, dim3(256), 0, \
+                     cur_stream(), (const short*)x.data_ptr(),               \
+                     (const unsigned char*)wq.data_ptr(),                    \
+                     scale.data_ptr<float>(), (short*)y.data_ptr(),          \
+                     SPLIT ? ws.data_ptr<float>() : nullptr, (int)M, (int)N, \
+                     (int)K)
+  if (S > 1) {
+    if (bm == 64) { W8G_LAUNCH(64, true); } else { W8G_LAUNCH(128, true); }
+    hipLaunchKernelGGL(linear_w8_gemm_combine,
+                       dim3((unsigned)((M * N / 4 + 255) / 256)), dim3(256), 0,
+                       cur_stream(), ws.data_ptr<float>(),
+                       scale.data_ptr<float>(), (short*)y.data_ptr(), M * N,
+                       (int)N, (int)S);
+  } else {
+    if (bm == 64) { W8G_LAUNCH(64, false); } else { W8G_LAUNCH(128, false); }
+  }
+#undef W8G_LAUNCH
   return y;
 }
 
@@ -1111,6 +1184,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv", &gemv);
   m.def("linear_w8", &linear_w8, py::arg("x"), py::arg("wq"), py::arg("scale"),
         py::arg("tile") = 0);
+  m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
+        py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("gemm_wgrad", &gemm_wgrad, py::arg("dy"), py::arg("x"),
         py::arg("out") = py::none());
   m.def("gemm_wgrad_grouped", &gemm_wgrad_grouped);

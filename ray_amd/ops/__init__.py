@@ -252,25 +252,61 @@ def linear_w8_ref(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor):
     return (x.double() @ w.t()).float()
 
 
+# (N, K) -> the largest row count that goes to linear_w8_gemm
+# (csrc/hip/linear_w8_gemm.hip) instead of dequantise + F.linear. A shape
+# enters, with the largest M up to which it won at every measured M
+# (64, 128, 256, 512, 1024, 2048), only if the kernel's slowest repetition
+# beat the fallback's fastest in tools/linear_w8_bench.py --gemm (times in
+# the comments, µs at the listed M, kernel median / fallback median).
+# Shapes not listed keep the fallback.
+_W8_GEMM_TABLE: dict = {
+    # llama3-8b; all five won at every measured M, times at M = 2048
+    (6144, 4096): 2048,     # qkv:      117.0 /  181.1 (M = 64:  21.4 /  115.7)
+    (4096, 4096): 2048,     # o_proj:    76.2 /  128.2 (M = 64:  14.2 /   81.5)
+    (14336, 4096): 2048,    # gate/up:  321.7 /  454.8 (M = 64:  29.9 /  320.2)
+    (4096, 14336): 2048,    # down:     287.5 /  494.4 (M = 64:  29.0 /  342.4)
+    (128256, 4096): 2048,   # lm_head: 3263.2 / 4173.3 (M = 64: 190.5 / 2810.4)
+    # llama3-1b, likewise
+    (3072, 2048): 2048,     # qkv:       40.3 /   59.6 (M = 64:  10.5 /   41.6)
+    (2048, 2048): 2048,     # o_proj:    24.7 /   45.4 (M = 64:  10.1 /   37.5)
+    (8192, 2048): 2048,     # gate/up:   82.4 /  120.4 (M = 64:  13.5 /   79.6)
+    (2048, 8192): 2048,     # down:      76.8 /  134.8 (M = 64:  16.0 /   87.1)
+    (128256, 2048): 2048,   # lm_head: 1654.4 / 2139.1 (M = 64:  85.6 / 1431.4)
+}
+
+# test hook: send every qualifying call of 33+ rows to the kernel
+_W8_GEMM_FORCE = False
+
+
 def linear_w8(x: torch.Tensor, wq: torch.Tensor,
               scale: torch.Tensor) -> torch.Tensor:
     """x[..., K] · (wq[N, K] * scale[N])^T with fp8 weights (see
-    quantize_weight_fp8). bf16 GPU activations of at most 32 rows with
-    K % 128 == 0 and grad off run the skinny-GEMM kernel, which reads one
-    byte per weight. Everything else (CPU, prefill chunks, odd shapes, grad
-    on) dequantises the weight to the activation dtype and calls F.linear:
-    there is no fp8 prefill GEMM, prefill pays a dequantisation per
-    call."""
+    quantize_weight_fp8). bf16 GPU activations with K % 128 == 0, grad off
+    and contiguous, 16-byte-aligned operands run a kernel that reads one
+    byte per weight: the skinny-GEMM kernel for at most 32 rows, and the
+    W8A16 GEMM kernel (linear_w8_gemm: prefill chunks, decode steps of more
+    than 32 sequences) for 33 rows up to the limit _W8_GEMM_TABLE lists for
+    the shape (N, K), N % 128 == 0. Everything else (CPU, shapes and row
+    counts that are not listed, odd shapes, grad on) dequantises the weight
+    to the activation dtype and calls F.linear, which costs a bf16 copy of
+    the weight per call."""
     K = x.shape[-1]
     rows = x.numel() // K
     if x.is_cuda:
         _require_ext("linear_w8")
-        if (x.dtype == torch.bfloat16 and 1 <= rows <= 32 and K % 128 == 0
+        N = wq.shape[0]
+        gemm = (rows > 32 and N % 128 == 0 and
+                (_W8_GEMM_FORCE or rows <= _W8_GEMM_TABLE.get((N, K), 0)))
+        if (x.dtype == torch.bfloat16 and (1 <= rows <= 32 or gemm)
+                and K % 128 == 0
                 and not torch.is_grad_enabled() and wq.is_contiguous()
                 and wq.data_ptr() % 16 == 0):
             x2 = x.reshape(rows, K).contiguous()
             if x2.data_ptr() % 16 == 0:
-                y = _K.linear_w8(x2, wq, scale.contiguous())
+                if gemm:
+                    y = _K.linear_w8_gemm(x2, wq, scale.contiguous())
+                else:
+                    y = _K.linear_w8(x2, wq, scale.contiguous())
                 return y.view(*x.shape[:-1], wq.shape[0])
     w = (wq.float() * scale[:, None]).to(x.dtype)
     return torch.nn.functional.linear(x, w)

@@ -5,7 +5,7 @@ for a shared prefix plus a tail, cold and warm.
 
     python tools/paged_prefill_bench.py [--shapes 3072:1024,0:4096]
         [--model llama3-8b] [--prefix 2048] [--tail 128] [--skip-model]
-        [--kv-dtype bf16,fp8]
+        [--kv-dtype bf16,fp8] [--weight-dtype bf16|fp8]
 
 (a) reports median [min, max] microseconds per call over --reps timed
 repetitions of --iters back-to-back calls after warm-up, and the
@@ -16,6 +16,8 @@ cold and once more (with another tail) warm.
 With --kv-dtype fp8 the kernel rows run on an fp8 cache (the composite
 reads the dequantised values as bf16, which is exact), and the model
 rows are cold and warm prefill into an fp8 pool.
+--weight-dtype fp8 quantises the model's projections and lm_head to fp8
+(quantize_linears_fp8) before any decoder is built.
 """
 import argparse
 import os
@@ -147,6 +149,11 @@ def bench_model(args, dev, kv_dtypes):
         model = LlamaModel(cfg, dtype=torch.bfloat16).eval()
     model.cosT = model.cosT.to(dev)
     model.sinT = model.sinT.to(dev)
+    if args.weight_dtype == "fp8":
+        from ray_amd.models.llama import quantize_linears_fp8
+
+        quantize_linears_fp8(model)
+        print("# weight_dtype=fp8")
     if "bf16" not in kv_dtypes:
         return bench_model_fp8(args, dev, model)
     n = args.prefix + args.tail
@@ -221,6 +228,7 @@ def main():
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--kv-dtype", default="bf16",
                     help="comma-separated cache formats: bf16, fp8")
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"])
     args = ap.parse_args()
     kv_dtypes = args.kv_dtype.split(",")
     assert set(kv_dtypes) <= {"bf16", "fp8"}, kv_dtypes
