@@ -26,6 +26,7 @@
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
+#include "hip/sample.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                       \
@@ -346,6 +347,64 @@ at::Tensor linear_w8(at::Tensor x, at::Tensor wq, at::Tensor scale,
   }
 #undef W8_LAUNCH
   return y;
+}
+
+// ---------------- Batched token sampling ----------------
+
+// One token per row of logits[B, V] (bf16 or fp32, last dimension contiguous,
+// any row stride) under per-row temperature, top_k, top_p and random number
+// u; the rules are in csrc/hip/sample.hip. Returns (tokens int64 [B],
+// n_kept int32 [B]). One launch, no workspace, no host synchronisation.
+std::tuple<at::Tensor, at::Tensor> sample(at::Tensor logits,
+                                          at::Tensor temperature,
+                                          at::Tensor top_k, at::Tensor top_p,
+                                          at::Tensor u) {
+  TORCH_CHECK(logits.is_cuda(), "sample: logits must be on GPU");
+  TORCH_CHECK(logits.dim() == 2, "sample: logits must be [B, V]");
+  const long long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= (long long)SAMPLE_MAX_CHUNKS * SAMPLE_CHUNK,
+              "sample: V must be 1..", SAMPLE_MAX_CHUNKS * SAMPLE_CHUNK);
+  TORCH_CHECK(B < (1ll << 31), "sample: too many rows");
+  TORCH_CHECK(V == 1 || logits.stride(1) == 1,
+              "sample: the last dimension of logits must be contiguous");
+  const long long stride = B > 1 ? logits.stride(0) : 0;
+  TORCH_CHECK(stride >= 0, "sample: negative row stride");
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(is_bf16 || logits.scalar_type() == at::kFloat,
+              "sample: logits must be bf16 or fp32");
+  CHECK_IN(temperature); CHECK_IN(top_k); CHECK_IN(top_p); CHECK_IN(u);
+  TORCH_CHECK(temperature.scalar_type() == at::kFloat &&
+              top_p.scalar_type() == at::kFloat &&
+              u.scalar_type() == at::kFloat &&
+              top_k.scalar_type() == at::kInt,
+              "sample: temperature, top_p, u must be fp32 and top_k int32");
+  TORCH_CHECK(temperature.numel() == B && top_k.numel() == B &&
+              top_p.numel() == B && u.numel() == B,
+              "sample: per-row parameters must have B elements");
+  auto tokens = at::empty({B}, logits.options().dtype(at::kLong));
+  auto n_kept = at::empty({B}, logits.options().dtype(at::kInt));
+  if (B == 0) return {tokens, n_kept};
+  // 16-byte loads need every row start on a 16-byte boundary
+  const long long esz = is_bf16 ? 2 : 4;
+  const int vec = aligned16(logits) && (stride * esz) % 16 == 0;
+#define SAMPLE_LAUNCH(T, ONCHIP)                                             \
+  hipLaunchKernelGGL((sample_kernel<T, ONCHIP>), dim3((unsigned)B),          \
+                     dim3(SAMPLE_THREADS), 0, cur_stream(),                  \
+                     (const T*)logits.data_ptr(), stride, (int)V, vec,       \
+                     temperature.data_ptr<float>(), top_k.data_ptr<int>(),   \
+                     top_p.data_ptr<float>(), u.data_ptr<float>(),           \
+                     (long long*)tokens.data_ptr<int64_t>(),                 \
+                     n_kept.data_ptr<int>())
+  if (!is_bf16) {
+    SAMPLE_LAUNCH(float, false);
+  } else if (vec && V <= SAMPLE_ONCHIP_CHUNKS * SAMPLE_CHUNK) {
+    SAMPLE_LAUNCH(short, true);
+  } else {
+    SAMPLE_LAUNCH(short, false);
+  }
+#undef SAMPLE_LAUNCH
+  HIP_CHECK_KERNEL();
+  return {tokens, n_kept};
 }
 
 // ---------------- FP8 weight-only GEMM (33+ rows) ----------------
@@ -1186,6 +1245,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tile") = 0);
   m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
+  m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),
+        py::arg("top_k"), py::arg("top_p"), py::arg("u"));
   m.def("gemm_wgrad", &gemm_wgrad, py::arg("dy"), py::arg("x"),
         py::arg("out") = py::none());
   m.def("gemm_wgrad_grouped", &gemm_wgrad_grouped);

@@ -7,12 +7,14 @@ sampling) is the real one.
 """
 from __future__ import annotations
 
+import random
 import time
 from dataclasses import dataclass, field
 from typing import List, Optional
 
 import torch
 
+from ray_amd import ops
 from ray_amd.models.llama import (
     CONFIGS,
     BatchedDecoder,
@@ -55,6 +57,70 @@ class LLMConfig:
     # scale per output channel (ops.LinearW8), and decode reads them with
     # the fp8 skinny-GEMM kernel. Activations stay in the model dtype.
     weight_dtype: str = "auto"
+    # Sampling defaults of a request (each can be given per request).
+    # top_k: keep the k largest logits, ties at the k-th kept (0: off).
+    # top_p: then keep the smallest set of largest logits whose mass reaches
+    # top_p (1: off). seed: the request draws from its own
+    # random.Random(seed), so its tokens do not depend on what else is in
+    # the batch (None: the engine's generator). A request that sets none of
+    # the three samples as before (argmax or torch.multinomial); the others
+    # go through ops.sample, whose rules are in ops.sample_ref.
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: Optional[int] = None
+    # ContinuousBatchingEngine only: sample the whole batch with one
+    # ops.sample call per step. The step then makes one host-to-device copy
+    # (the parameters of all slots, from one pinned tensor) and one
+    # device-to-host copy (the tokens) instead of one synchronisation and
+    # two scalar writes per slot.
+    device_sampling: bool = False
+
+    def __post_init__(self):
+        _check_sampling(self.top_k, self.top_p)
+
+
+def _check_sampling(top_k, top_p):
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    if not 0.0 <= top_p <= 1.0:
+        raise ValueError(f"top_p must be in [0, 1], got {top_p!r}")
+
+
+_U_MAX = 1.0 - 2.0 ** -24  # the largest fp32 below 1
+
+
+class _Sampling:
+    """What the engines share: per-request sampling parameters and the
+    per-row path through ops.sample."""
+
+    def _init_sampling(self):
+        self._rng = random.Random()
+
+    def _request_sampling(self, temperature, top_k, top_p, seed) -> dict:
+        c = self.config
+        top_k = c.top_k if top_k is None else top_k
+        top_p = c.top_p if top_p is None else top_p
+        seed = c.seed if seed is None else seed
+        _check_sampling(top_k, top_p)
+        rng = None if seed is None else random.Random(seed)
+        return {
+            "temperature": float(c.temperature if temperature is None
+                                 else temperature),
+            "top_k": int(top_k), "top_p": float(top_p), "rng": rng,
+            # False: the argmax / torch.multinomial path of _sample
+            "filtered": top_k > 0 or top_p < 1.0 or rng is not None,
+        }
+
+    def _next_u(self, req: dict) -> float:
+        return min((req["rng"] or self._rng).random(), _U_MAX)
+
+    def _sample_request(self, logits: torch.Tensor, req: dict) -> int:
+        """One token for one request from its logits row [V]."""
+        if not req["filtered"]:
+            return self._sample(logits, req["temperature"])
+        tok = ops.sample(logits.view(1, -1), req["temperature"],
+                         req["top_k"], req["top_p"], self._next_u(req))
+        return int(tok.item())
 
 
 # LLMConfig.kv_cache_dtype -> page dtype (None: the model dtype)
@@ -76,9 +142,10 @@ def _fp8_weights(config: LLMConfig) -> bool:
     return config.weight_dtype.startswith("fp8")
 
 
-class LLMEngine:
+class LLMEngine(_Sampling):
     def __init__(self, config: LLMConfig):
         self.config = config
+        self._init_sampling()
         if _fp8_weights(config):
             raise ValueError("weight_dtype='fp8' needs "
                              "ContinuousBatchingEngine with kv_cache='paged'")
@@ -111,10 +178,10 @@ class LLMEngine:
 
     @torch.no_grad()
     def generate(self, prompt_ids: List[int], max_new_tokens: int = 32,
-                 temperature: Optional[float] = None) -> dict:
-        temperature = (
-            self.config.temperature if temperature is None else temperature
-        )
+                 temperature: Optional[float] = None,
+                 top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 seed: Optional[int] = None) -> dict:
+        req = self._request_sampling(temperature, top_k, top_p, seed)
         cfg = self.model_cfg
         prompt_ids = [t % cfg.vocab_size for t in prompt_ids][: self.max_T - max_new_tokens - 1]
         toks = torch.tensor([prompt_ids], device=self.device)
@@ -140,7 +207,7 @@ class LLMEngine:
         pos = len(prompt_ids)
         t0 = time.perf_counter()
         for _ in range(max_new_tokens):
-            nxt = self._sample(logits[0], temperature)
+            nxt = self._sample_request(logits[0], req)
             out.append(nxt)
             if pos >= self.max_T - 1:
                 break
@@ -183,7 +250,7 @@ class _ViewCache:
         return self.k_buf[:, :, : self.len], self.v_buf[:, :, : self.len]
 
 
-class ContinuousBatchingEngine:
+class ContinuousBatchingEngine(_Sampling):
     """Continuous batching (the vLLM-style loop the reference's serve
     LLM rides on): up to max_batch_size sequences decode together in a
     shared batched KV cache; finished sequences retire and queued
@@ -192,6 +259,7 @@ class ContinuousBatchingEngine:
 
     def __init__(self, config: LLMConfig):
         self.config = config
+        self._init_sampling()
         cfg = CONFIGS[config.model_id]
         self.model_cfg = cfg
         self.device = (
@@ -255,6 +323,17 @@ class ContinuousBatchingEngine:
                                 device=self.device)
         self._pos = torch.zeros(self.B, dtype=torch.long,
                                 device=self.device)
+        if config.device_sampling:
+            # rows: temperature, top_k, top_p, u, position; the fp32 rows
+            # are int32 words viewed as float. One pinned tensor, so a step
+            # sends all of it in one copy.
+            self._stage = torch.zeros(
+                5, self.B, dtype=torch.int32,
+                pin_memory=self.device.type == "cuda")
+            self._stage_i = self._stage.numpy()
+            self._stage_f = self._stage.view(torch.float32).numpy()
+            self._params = torch.zeros(5, self.B, dtype=torch.int32,
+                                       device=self.device)
         self.stats = {"requests": 0, "tokens_generated": 0,
                       "decode_steps": 0}
         self.stats["weight_bytes"] = sum(
@@ -278,7 +357,10 @@ class ContinuousBatchingEngine:
         return min(prompt_len + max_new_tokens, self.max_T)
 
     def submit(self, prompt_ids: List[int], max_new_tokens: int = 32,
-               temperature: Optional[float] = None) -> int:
+               temperature: Optional[float] = None,
+               top_k: Optional[int] = None, top_p: Optional[float] = None,
+               seed: Optional[int] = None) -> int:
+        sampling = self._request_sampling(temperature, top_k, top_p, seed)
         rid = self._next_id
         self._next_id += 1
         cfg = self.model_cfg
@@ -297,8 +379,7 @@ class ContinuousBatchingEngine:
         self._queue.append({
             "id": rid, "prompt": prompt,
             "max_new_tokens": max_new_tokens,
-            "temperature": (self.config.temperature
-                            if temperature is None else temperature),
+            **sampling,
         })
         self.stats["requests"] += 1
         return rid
@@ -328,7 +409,14 @@ class ContinuousBatchingEngine:
                     logits = self.decoder.prefill_slot(slot, toks, reserve)
                 else:
                     logits = self.decoder.prefill_slot(slot, toks)
-            first = self._sample(logits, req["temperature"])
+            if self.config.device_sampling:
+                tok = ops.sample(logits.view(1, -1), req["temperature"],
+                                 req["top_k"], req["top_p"],
+                                 self._next_u(req))
+                self._tok[slot : slot + 1].copy_(tok)
+                first = int(tok.item())
+            else:
+                first = self._sample_request(logits, req)
             req.update({
                 "out": [first],
                 "pos": len(req["prompt"]),  # next decode position
@@ -366,15 +454,21 @@ class ContinuousBatchingEngine:
         if not active:
             out, self._finished = self._finished, []
             return out
+        if self.config.device_sampling:
+            sampled = self._decode_and_sample(active)
+        else:
+            for s in active:
+                r = self._slots[s]
+                self._tok[s] = r["out"][-1]
+                self._pos[s] = r["pos"]
+                self.decoder.set_slot_len(s, r["pos"] + 1)  # attend new tok
+            logits = self.decoder.decode(self._tok, self._pos)
         for s in active:
             r = self._slots[s]
-            self._tok[s] = r["out"][-1]
-            self._pos[s] = r["pos"]
-            self.decoder.set_slot_len(s, r["pos"] + 1)  # attend new tok
-        logits = self.decoder.decode(self._tok, self._pos)
-        for s in active:
-            r = self._slots[s]
-            nxt = self._sample(logits[s], r["temperature"])
+            if self.config.device_sampling:
+                nxt = sampled[s]
+            else:
+                nxt = self._sample_request(logits[s], r)
             r["out"].append(nxt)
             r["pos"] += 1
             if (len(r["out"]) >= r["max_new_tokens"]
@@ -383,6 +477,30 @@ class ContinuousBatchingEngine:
         self.stats["decode_steps"] += 1
         out, self._finished = self._finished, []
         return out
+
+    def _decode_and_sample(self, active: List[int]) -> List[int]:
+        """device_sampling: one decode step and one ops.sample call for the
+        whole batch. self._tok already holds every active slot's last token
+        on the device (written by the previous call, or by _admit), so the
+        host sends only the parameters and reads back only the tokens.
+        Inactive slots have temperature 0 and their tokens are ignored."""
+        si, sf = self._stage_i, self._stage_f
+        sf[0, :] = 0.0
+        for s in active:
+            r = self._slots[s]
+            sf[0, s] = r["temperature"]
+            si[1, s] = r["top_k"]
+            sf[2, s] = r["top_p"]
+            sf[3, s] = self._next_u(r)
+            si[4, s] = r["pos"]
+            self.decoder.set_slot_len(s, r["pos"] + 1)  # attend new tok
+        self._params.copy_(self._stage, non_blocking=True)
+        self._pos.copy_(self._params[4])
+        logits = self.decoder.decode(self._tok, self._pos)
+        pf = self._params.view(torch.float32)
+        toks = ops.sample(logits, pf[0], self._params[1], pf[2], pf[3])
+        self._tok.copy_(toks)
+        return toks.tolist()
 
     def has_work(self) -> bool:
         return bool(self._queue) or any(

@@ -39,10 +39,12 @@ class LLMServer:
             await asyncio.sleep(0)
         self._pump_task = None
 
-    async def _generate_cb(self, prompt_ids, max_new_tokens, temperature):
+    async def _generate_cb(self, prompt_ids, max_new_tokens, temperature,
+                           top_k, top_p, seed):
         import asyncio
 
-        rid = self.engine.submit(prompt_ids, max_new_tokens, temperature)
+        rid = self.engine.submit(prompt_ids, max_new_tokens, temperature,
+                                 top_k, top_p, seed)
         fut = asyncio.get_running_loop().create_future()
         self._futures[rid] = fut
         if self._pump_task is None or self._pump_task.done():
@@ -51,12 +53,16 @@ class LLMServer:
         return {"token_ids": token_ids, "decode_tok_s": 0.0}
 
     async def generate(self, prompt_ids, max_new_tokens: int = 32,
-                       temperature: float = 0.0):
+                       temperature: float = 0.0,
+                       top_k: Optional[int] = None,
+                       top_p: Optional[float] = None,
+                       seed: Optional[int] = None):
         if self._batching == "continuous":
             return await self._generate_cb(
-                prompt_ids, max_new_tokens, temperature
+                prompt_ids, max_new_tokens, temperature, top_k, top_p, seed
             )
-        return self.engine.generate(prompt_ids, max_new_tokens, temperature)
+        return self.engine.generate(prompt_ids, max_new_tokens, temperature,
+                                    top_k, top_p, seed)
 
     def stats(self):
         return dict(self.engine.stats)
@@ -70,6 +76,9 @@ class LLMServer:
             prompt_ids,
             int(body.get("max_tokens", 32)),
             float(body.get("temperature", 0.0)),
+            None if body.get("top_k") is None else int(body["top_k"]),
+            None if body.get("top_p") is None else float(body["top_p"]),
+            None if body.get("seed") is None else int(body["seed"]),
         )
         return {
             "id": "cmpl-ray-amd",

@@ -1200,3 +1200,82 @@ def paged_attention_prefill(q, k_cache, v_cache, block_table, ctx_lens,
     _require_ext("paged_attention_prefill")
     return _K.paged_attn_prefill(q, k_cache, v_cache, block_table, ctx_lens,
                                  q_lens, float(k_scale), float(v_scale))
+
+
+# --------------------------------------------------------------------------
+# Token sampling: temperature, top-k, top-p, inverse-CDF draw
+# --------------------------------------------------------------------------
+
+
+def _sample_params(B, device, temperature, top_k, top_p, u):
+    def row(v, dtype):
+        if not torch.is_tensor(v):
+            return torch.full((B,), v, dtype=dtype, device=device)
+        return v.to(device=device, dtype=dtype).expand(B).contiguous()
+
+    return (row(temperature, torch.float32), row(top_k, torch.int32),
+            row(top_p, torch.float32), row(u, torch.float32))
+
+
+def sample_ref(logits: torch.Tensor, temperature, top_k, top_p, u,
+               return_kept: bool = False):
+    """fp64 reference of `sample`, on the logits' device. Per row, with x the
+    logits [V] (-inf allowed and never chosen):
+
+    1. temperature <= 0: the lowest index of the maximum; n_kept = 1.
+    2. 0 < top_k < V: keep x >= the k-th largest value (ties kept).
+    3. p_i = exp((x_i - max x) / temperature) on kept tokens, else 0.
+    4. top_p < 1: with Z1 the kept mass, keep x >= tau, tau the largest
+       value with sum{p_i : x_i >= tau} >= top_p * Z1 (ties kept; the
+       maximum always stays).
+    5. With Z the kept mass, the token is the smallest kept index i with
+       sum{p_j : j <= i} > u * Z, or the last kept index if there is none.
+
+    Returns tokens int64 [B], and n_kept int32 [B] with return_kept."""
+    B, V = logits.shape
+    temperature, top_k, top_p, u = _sample_params(
+        B, logits.device, temperature, top_k, top_p, u)
+    tokens = torch.empty(B, dtype=torch.long, device=logits.device)
+    n_kept = torch.ones(B, dtype=torch.int32, device=logits.device)
+    for r in range(B):
+        x = logits[r].double()
+        T, k, tp = float(temperature[r]), int(top_k[r]), float(top_p[r])
+        if T <= 0:
+            tokens[r] = int((x == x.max()).nonzero()[0])
+            continue
+        keep = torch.ones(V, dtype=torch.bool, device=x.device)
+        if 0 < k < V:
+            keep = x >= torch.sort(x, descending=True).values[k - 1]
+        p = torch.where(keep, torch.exp((x - x.max()) / T), 0.0)
+        if tp < 1:
+            xs, order = torch.sort(x, descending=True)
+            reach = (torch.cumsum(p[order], 0) >= tp * p.sum()).nonzero()
+            tau = xs[int(reach[0])] if tp > 0 and reach.numel() else xs[0]
+            keep &= x >= tau
+            p = torch.where(keep, p, 0.0)
+        above = (torch.cumsum(p, 0) > float(u[r]) * p.sum()) & keep
+        kept_idx = keep.nonzero()
+        tokens[r] = int(above.nonzero()[0]) if above.any() else int(
+            kept_idx[-1])
+        n_kept[r] = int(keep.sum())
+    return (tokens, n_kept) if return_kept else tokens
+
+
+def sample(logits: torch.Tensor, temperature, top_k, top_p, u,
+           return_kept: bool = False):
+    """One token per row of logits [B, V] under per-row temperature [B],
+    top_k [B], top_p [B] and random number u [B] in [0, 1) (Python scalars
+    broadcast); the rules are in sample_ref. The draw is an inverse CDF in
+    index order with u an input, so the result is a pure function of the
+    arguments. bf16 and fp32 GPU logits whose last dimension is contiguous
+    (any row stride) run the one-launch HIP kernel (csrc/hip/sample.hip);
+    everything else runs sample_ref. Returns tokens int64 [B], and with
+    return_kept also n_kept int32 [B], the tokens that survived the filters."""
+    if (logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float32)
+            and logits.dim() == 2
+            and (logits.shape[1] == 1 or logits.stride(1) == 1)):
+        _require_ext("sample")
+        tokens, n_kept = _K.sample(logits, *_sample_params(
+            logits.shape[0], logits.device, temperature, top_k, top_p, u))
+        return (tokens, n_kept) if return_kept else tokens
+    return sample_ref(logits, temperature, top_k, top_p, u, return_kept)
