@@ -23,6 +23,7 @@
 #include "hip/gemv.hip"
 #include "hip/linear_w8.hip"
 #include "hip/linear_w8_gemm.hip"
+#include "hip/linear_w4.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
@@ -347,6 +348,121 @@ at::Tensor linear_w8(at::Tensor x, at::Tensor wq, at::Tensor scale,
   }
 #undef W8_LAUNCH
   return y;
+}
+
+// ---------------- MXFP4 weight-only skinny GEMM (decode linear) ----------------
+
+static void check_mxfp4(const at::Tensor& wq, const at::Tensor& scales,
+                        long long* N, long long* K, const char* who) {
+  CHECK_IN(wq); CHECK_IN(scales);
+  TORCH_CHECK(wq.scalar_type() == at::kByte && scales.scalar_type() == at::kByte,
+              who, ": wq and scales must be uint8");
+  TORCH_CHECK(wq.dim() == 2 && scales.dim() == 2, who,
+              ": wq must be [N, K/2] and scales [N, K/32]");
+  *N = wq.size(0);
+  *K = wq.size(1) * 2;
+  TORCH_CHECK(*N >= 1 && *N < (1ll << 31) - 128, who, ": bad N");
+  TORCH_CHECK(*K >= 32 && *K % 32 == 0 && *K < (1ll << 31), who,
+              ": K must be a multiple of 32");
+  TORCH_CHECK(scales.size(0) == *N && scales.size(1) == *K / 32, who,
+              ": scales must be [N, K/32]");
+  TORCH_CHECK(aligned16(wq), who, ": wq must be 16-byte aligned");
+}
+
+// y[M,N] = x[M,K] · dequant(wq[N,K/2], scales[N,K/32])^T (csrc/hip/
+// linear_w4.hip); x bf16, wq and scales uint8. `tile` picks the channels per
+// block (64 or 128; 0: 128) and `split` the slices of K (1, 2, 4 or 8;
+// 0: the rule below). The overrides are there for tools/linear_w8_bench.py
+// and the tests; the result depends on neither.
+at::Tensor linear_w4(at::Tensor x, at::Tensor wq, at::Tensor scales,
+                     int64_t tile, int64_t split) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "linear_w4: x must be bf16");
+  TORCH_CHECK(x.dim() == 2, "linear_w4: x must be [M, K]");
+  long long N, K;
+  check_mxfp4(wq, scales, &N, &K, "linear_w4");
+  const long long M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 32, "linear_w4: rows must be 1..32");
+  TORCH_CHECK(x.size(1) == K && K % 128 == 0,
+              "linear_w4: K must be a multiple of 128 and match x");
+  // a row of scales is then a whole number of dwords
+  TORCH_CHECK(aligned16(x) && (uintptr_t)scales.data_ptr() % 4 == 0,
+              "linear_w4: x must be 16-byte and scales 4-byte aligned");
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128,
+              "linear_w4: tile must be 0, 64 or 128");
+  TORCH_CHECK(split == 0 || split == 1 || split == 2 || split == 4 ||
+              split == 8, "linear_w4: split must be 0, 1, 2, 4 or 8");
+  // x-bytes per weight byte is 4*M/tile: 128 channels keep it at 1 or less.
+  // 64 would do up to 16 rows with twice the blocks, but measured slower at
+  // every shape and row count of tools/linear_w8_bench.py (PERFORMANCE.md).
+  const int C = tile ? (int)tile : 128;
+  const long long nb = (N + C - 1) / C;
+  long long S = split;
+  if (S == 0) {
+    // the fewest slices that give every CU a block, while the fp32 partials
+    // (4 bytes written and 4 read per element and slice) stay below the
+    // weight bytes: S*M*N*8 <= N*K/2
+    const long long cus =
+        at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    S = 1;
+    while (S < 8 && nb * S < cus && 2 * S * M * 16 <= K) S *= 2;
+  }
+  auto y = at::empty({M, N}, x.options());
+  at::Tensor ws;
+  if (S > 1) ws = at::empty({S, M, N}, x.options().dtype(at::kFloat));
+  const dim3 grid((unsigned)nb, (unsigned)S);
+#define W4_LAUNCH(MT, WV, GPB)                                               \
+  hipLaunchKernelGGL((linear_w4_bf16_kernel<MT, WV, GPB>), grid,             \
+                     dim3(64 * WV), 0, cur_stream(),                         \
+                     (const short*)x.data_ptr(),                             \
+                     (const unsigned char*)wq.data_ptr(),                    \
+                     (const unsigned char*)scales.data_ptr(),                \
+                     (short*)y.data_ptr(),                                   \
+                     GPB < 8 ? ws.data_ptr<float>() : nullptr, (int)M,       \
+                     (int)N, (int)K)
+#define W4_LAUNCH_S(MT, WV)                                                  \
+  switch (S) {                                                               \
+    case 1: W4_LAUNCH(MT, WV, 8); break;                                     \
+    case 2: W4_LAUNCH(MT, WV, 4); break;                                     \
+    case 4: W4_LAUNCH(MT, WV, 2); break;                                     \
+    default: W4_LAUNCH(MT, WV, 1); break;                                    \
+  }
+  if (M <= 16) {
+    if (C == 64) { W4_LAUNCH_S(1, 4); } else { W4_LAUNCH_S(1, 8); }
+  } else {
+    if (C == 64) { W4_LAUNCH_S(2, 4); } else { W4_LAUNCH_S(2, 8); }
+  }
+#undef W4_LAUNCH_S
+#undef W4_LAUNCH
+  if (S > 1) {
+    const long long total = M * N;
+    const dim3 cgrid((unsigned)((total + 255) / 256));
+#define W4_COMBINE(SS)                                                       \
+  hipLaunchKernelGGL(linear_w4_combine<SS>, cgrid, dim3(256), 0,             \
+                     cur_stream(), ws.data_ptr<float>(),                     \
+                     (short*)y.data_ptr(), total)
+    if (S == 2) { W4_COMBINE(2); } else if (S == 4) { W4_COMBINE(4); }
+    else { W4_COMBINE(8); }
+#undef W4_COMBINE
+  }
+  HIP_CHECK_KERNEL();
+  return y;
+}
+
+// bf16 [N, K] of an MXFP4 weight, exact; K % 32 == 0.
+at::Tensor dequant_mxfp4(at::Tensor wq, at::Tensor scales) {
+  long long N, K;
+  check_mxfp4(wq, scales, &N, &K, "dequant_mxfp4");
+  auto out = at::empty({N, K}, wq.options().dtype(at::kBFloat16));
+  const long long blocks = N * (K / 32);
+  TORCH_CHECK((blocks + 255) / 256 < (1ll << 31), "dequant_mxfp4: too large");
+  hipLaunchKernelGGL(dequant_mxfp4_kernel, dim3((unsigned)((blocks + 255) / 256)),
+                     dim3(256), 0, cur_stream(),
+                     (const unsigned char*)wq.data_ptr(),
+                     (const unsigned char*)scales.data_ptr(),
+                     (short*)out.data_ptr(), blocks);
+  HIP_CHECK_KERNEL();
+  return out;
 }
 
 // ---------------- Batched token sampling ----------------
@@ -1243,6 +1359,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv", &gemv);
   m.def("linear_w8", &linear_w8, py::arg("x"), py::arg("wq"), py::arg("scale"),
         py::arg("tile") = 0);
+  m.def("linear_w4", &linear_w4, py::arg("x"), py::arg("wq"),
+        py::arg("scales"), py::arg("tile") = 0, py::arg("split") = 0);
+  m.def("dequant_mxfp4", &dequant_mxfp4, py::arg("wq"), py::arg("scales"));
   m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),

@@ -22,6 +22,7 @@ from ray_amd.models.llama import (
     KVCache,
     LlamaModel,
     quantize_linears_fp8,
+    quantize_linears_mxfp4,
 )
 
 
@@ -55,7 +56,10 @@ class LLMConfig:
     # "auto" or "bf16" (the model dtype) or "fp8" ("fp8_e4m3" is the same):
     # every projection and lm_head hold one byte per weight plus an fp32
     # scale per output channel (ops.LinearW8), and decode reads them with
-    # the fp8 skinny-GEMM kernel. Activations stay in the model dtype.
+    # the fp8 skinny-GEMM kernel. "mxfp4": they hold OCP MXFP4 instead, two
+    # e2m1 elements per byte and one e8m0 scale byte per 32 of them, 17/32
+    # byte per weight (ops.LinearW4), read by the W4A16 skinny-GEMM kernel.
+    # Activations stay in the model dtype.
     weight_dtype: str = "auto"
     # Sampling defaults of a request (each can be given per request).
     # top_k: keep the k largest logits, ties at the k-th kept (0: off).
@@ -131,23 +135,27 @@ _KV_CACHE_DTYPES = {
     "fp8_e4m3": torch.float8_e4m3fn,
 }
 
-_WEIGHT_DTYPES = ("auto", "bf16", "fp8", "fp8_e4m3")
+_WEIGHT_DTYPES = ("auto", "bf16", "fp8", "fp8_e4m3", "mxfp4")
 
 
-def _fp8_weights(config: LLMConfig) -> bool:
+def _quantized_weights(config: LLMConfig):
+    """None for model-dtype weights, else "fp8" or "mxfp4"."""
     if config.weight_dtype not in _WEIGHT_DTYPES:
         raise ValueError(
             f"weight_dtype must be one of {sorted(_WEIGHT_DTYPES)}, got "
             f"{config.weight_dtype!r}")
-    return config.weight_dtype.startswith("fp8")
+    if config.weight_dtype.startswith("fp8"):
+        return "fp8"
+    return "mxfp4" if config.weight_dtype == "mxfp4" else None
 
 
 class LLMEngine(_Sampling):
     def __init__(self, config: LLMConfig):
         self.config = config
         self._init_sampling()
-        if _fp8_weights(config):
-            raise ValueError("weight_dtype='fp8' needs "
+        wq = _quantized_weights(config)
+        if wq:
+            raise ValueError(f"weight_dtype='{wq}' needs "
                              "ContinuousBatchingEngine with kv_cache='paged'")
         cfg = CONFIGS[config.model_id]
         self.model_cfg = cfg
@@ -293,10 +301,14 @@ class ContinuousBatchingEngine(_Sampling):
         kv_dtype = _KV_CACHE_DTYPES[config.kv_cache_dtype]
         if kv_dtype == torch.float8_e4m3fn and not self._paged:
             raise ValueError("kv_cache_dtype='fp8' needs kv_cache='paged'")
-        if _fp8_weights(config):
+        wq = _quantized_weights(config)
+        if wq:
             if not self._paged:
-                raise ValueError("weight_dtype='fp8' needs kv_cache='paged'")
-            quantize_linears_fp8(self.model)
+                raise ValueError(f"weight_dtype='{wq}' needs kv_cache='paged'")
+            if wq == "fp8":
+                quantize_linears_fp8(self.model)
+            else:
+                quantize_linears_mxfp4(self.model)
         if self._paged:
             from ray_amd.llm.paged import PagedDecoder
 

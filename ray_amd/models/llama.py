@@ -50,11 +50,16 @@ CONFIGS = {
 }
 
 
+# weight-only quantised projections: no `.weight`, their own kernels
+_QUANT_LINEARS = (ops.LinearW8, ops.LinearW4)
+
+
 def proj(mod, x, lin=None):
     """The projection `mod` applied to x. `lin(x, weight)` overrides the
     matmul of a bf16 Linear (decode paths pass the GEMV fast path); an
-    ops.LinearW8 always runs its own fp8-weight linear."""
-    if lin is None or isinstance(mod, ops.LinearW8):
+    ops.LinearW8 or ops.LinearW4 always runs its own quantised-weight
+    linear."""
+    if lin is None or isinstance(mod, _QUANT_LINEARS):
         return mod(x)
     return lin(x, mod.weight)
 
@@ -66,11 +71,21 @@ def quantize_linears_fp8(model: "LlamaModel") -> "LlamaModel":
     quantised from the embedding's values and no longer shares them. The
     model then serves inference only, through PagedDecoder or its own
     forward."""
+    return _quantize_linears(model, ops.LinearW8)
+
+
+def quantize_linears_mxfp4(model: "LlamaModel") -> "LlamaModel":
+    """quantize_linears_fp8 with ops.LinearW4 modules: MXFP4 weights, two
+    e2m1 elements per byte and one e8m0 scale byte per 32 of them."""
+    return _quantize_linears(model, ops.LinearW4)
+
+
+def _quantize_linears(model, cls):
     def swap(parent, names):
         for name in names:
             if hasattr(parent, name):
                 setattr(parent, name,
-                        ops.LinearW8.from_linear(getattr(parent, name)))
+                        cls.from_linear(getattr(parent, name)))
 
     for layer in model.layers:
         swap(layer.attn, ("qkv_proj", "q_proj", "k_proj", "v_proj", "o_proj"))
@@ -141,7 +156,7 @@ class Attention(nn.Module):
 
         if (flash(x) and self._fused_qkv and T % 256 == 0 and pos0 == 0
                 and ops._FUSED_QKV_ATTN
-                and not isinstance(self.qkv_proj, ops.LinearW8)
+                and not isinstance(self.qkv_proj, _QUANT_LINEARS)
                 and self.qkv_proj.weight.dtype == torch.bfloat16):
             # RoPE in place on the projection output, attention on its
             # q/k/v column sections, one packed gradient in backward
@@ -187,7 +202,7 @@ class MLP(nn.Module):
         )
 
     def forward(self, x):
-        if isinstance(self.gate_proj, ops.LinearW8):
+        if isinstance(self.gate_proj, _QUANT_LINEARS):
             return self.down_proj(
                 ops.swiglu(self.gate_proj(x), self.up_proj(x)))
         gate, up = ops.swiglu_mlp_in(

@@ -334,6 +334,113 @@ class LinearW8(torch.nn.Module):
 
 
 # --------------------------------------------------------------------------
+# MXFP4 weight-only linear for decode (csrc/hip/linear_w4.hip)
+# --------------------------------------------------------------------------
+
+# magnitude of e2m1 code 0..7; bit 3 of a nibble is the sign
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_BLOCK = 32
+
+
+def quantize_weight_mxfp4(w: torch.Tensor):
+    """[N, K] finite weights, K % 32 == 0 -> (wq uint8 [N, K/2], scales
+    uint8 [N, K/32]): OCP MXFP4. Each block of 32 consecutive k has one e8m0
+    scale code = clamp(floor(log2(amax)) - 2 + 127, 2, 252) (127 for a block
+    of zeros); its elements are w / 2^(code-127) rounded to the nearest
+    e2m1 value (0, 0.5, 1, 1.5, 2, 3, 4, 6 and a sign bit), ties to the even
+    mantissa, saturating at +-6. Element 2i is the low nibble of byte i and
+    2i+1 the high nibble. Codes stay inside 2..252 so that every
+    dequantised value is zero or a normal bf16; no NaN code is produced."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quantize_weight_mxfp4: K = {K} is not a multiple "
+                         f"of {MXFP4_BLOCK}")
+    wf = w.detach().double().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    # frexp: amax = m * 2^e with 0.5 <= m < 1, so floor(log2(amax)) = e - 1
+    e = torch.frexp(amax)[1].to(torch.int64) - 1
+    code = torch.where(amax > 0, (e - 2 + 127).clamp(2, 252),
+                       torch.full_like(e, 127))
+    v = (wf.abs() * torch.exp2((127 - code).double())[..., None]).clamp(max=6.0)
+    # the grid has step 0.5 below 2, 1 below 4 and 2 up to 6; torch.round
+    # rounds halves to even, which is the even mantissa on each step
+    q = torch.where(v < 2, torch.round(v * 2) / 2,
+                    torch.where(v < 4, torch.round(v), torch.round(v / 2) * 2))
+    grid = torch.tensor(_E2M1, dtype=torch.float64, device=w.device)
+    nib = torch.bucketize(q, grid).to(torch.uint8)
+    nib = nib | ((wf < 0) & (nib > 0)).to(torch.uint8) * 8
+    nib = nib.reshape(N, K // 2, 2)
+    return nib[..., 0] | (nib[..., 1] << 4), code.to(torch.uint8)
+
+
+def dequantize_mxfp4(wq: torch.Tensor, scales: torch.Tensor,
+                     dtype=torch.float32) -> torch.Tensor:
+    """The weight [N, K] that (wq, scales) of quantize_weight_mxfp4 stand
+    for, by table lookup; exact in bf16, fp32 and fp64."""
+    N = wq.shape[0]
+    nib = torch.stack((wq & 15, wq >> 4), dim=-1).reshape(N, -1).long()
+    # every product is exact in fp32 already (codes 2..252)
+    wide = torch.float64 if dtype == torch.float64 else torch.float32
+    table = torch.tensor(_E2M1 + tuple(-m for m in _E2M1), dtype=wide,
+                         device=wq.device)
+    scale = torch.exp2(scales.to(wide) - 127)
+    w = table[nib] * scale.repeat_interleave(MXFP4_BLOCK, dim=1)
+    return w.to(dtype)
+
+
+def linear_w4_ref(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor):
+    """fp64 reference of linear_w4, returned as fp32."""
+    w = dequantize_mxfp4(wq, scales, torch.float64)
+    return (x.double() @ w.t()).float()
+
+
+def linear_w4(x: torch.Tensor, wq: torch.Tensor,
+              scales: torch.Tensor) -> torch.Tensor:
+    """x[..., K] · dequant(wq[N, K/2], scales[N, K/32])^T with MXFP4 weights
+    (see quantize_weight_mxfp4). bf16 GPU activations of 1 to 32 rows with
+    K % 128 == 0, grad off and contiguous, 16-byte-aligned operands run the
+    W4A16 skinny-GEMM kernel, which reads 17/32 byte per weight. More rows
+    on the GPU (prefill) dequantise with one kernel pass and call F.linear.
+    Everything else (CPU, other dtypes, odd K, grad on) dequantises in torch
+    to the activation dtype and calls F.linear."""
+    K = x.shape[-1]
+    rows = x.numel() // K
+    if (x.is_cuda and x.dtype == torch.bfloat16 and rows >= 1
+            and K % 128 == 0 and not torch.is_grad_enabled()
+            and wq.is_contiguous() and scales.is_contiguous()
+            and wq.data_ptr() % 16 == 0 and scales.data_ptr() % 4 == 0):
+        _require_ext("linear_w4")
+        if rows > 32:
+            return torch.nn.functional.linear(x, _K.dequant_mxfp4(wq, scales))
+        x2 = x.reshape(rows, K).contiguous()
+        if x2.data_ptr() % 16 == 0:
+            y = _K.linear_w4(x2, wq, scales)
+            return y.view(*x.shape[:-1], wq.shape[0])
+    return torch.nn.functional.linear(x, dequantize_mxfp4(wq, scales, x.dtype))
+
+
+class LinearW4(torch.nn.Module):
+    """A bias-free linear whose weight is stored as MXFP4: two e2m1 elements
+    per byte plus one e8m0 scale byte per 32 (buffers `wq`, `scales`); it
+    holds no bf16 copy of the weight."""
+
+    def __init__(self, wq: torch.Tensor, scales: torch.Tensor):
+        super().__init__()
+        self.out_features, self.in_features = wq.shape[0], 2 * wq.shape[1]
+        self.register_buffer("wq", wq)
+        self.register_buffer("scales", scales)
+
+    @classmethod
+    def from_linear(cls, linear: torch.nn.Linear) -> "LinearW4":
+        if linear.bias is not None:
+            raise ValueError("LinearW4 has no bias")
+        return cls(*quantize_weight_mxfp4(linear.weight))
+
+    def forward(self, x):
+        return linear_w4(x, self.wq, self.scales)
+
+
+# --------------------------------------------------------------------------
 # Linear with a hand-written weight-gradient GEMM (csrc/hip/gemm_wgrad.hip)
 # --------------------------------------------------------------------------
 

@@ -4,14 +4,15 @@
     python tools/decode_bench.py [--model llama3-8b] [--tokens 128]
                                  [--ctx N[,N...]] [--paged] [--reps R]
                                  [--kv-dtype bf16,fp8]
-                                 [--weight-dtype bf16|fp8]
+                                 [--weight-dtype bf16|fp8|mxfp4]
 
 --ctx N starts decoding at context length N (default 64, i.e. tokens
 64..72+tokens); --paged adds a row per batch for the graph-captured
 PagedDecoder (paged KV cache + fused decode attention) at the same
 positions, once per --kv-dtype (fp8: one-byte OCP e4m3fn pages).
 --weight-dtype fp8 quantises the model's projections and lm_head to fp8
-(quantize_linears_fp8) before any decoder is built.
+(quantize_linears_fp8), mxfp4 to OCP MXFP4 (quantize_linears_mxfp4), before
+any decoder is built.
 """
 import argparse
 import os
@@ -23,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from ray_amd.models.llama import (CONFIGS, GraphedDecoder, LlamaModel,
-                                  quantize_linears_fp8)
+                                  quantize_linears_fp8,
+                                  quantize_linears_mxfp4)
 
 
 def bench(dec, cfg, B, n_tokens, prefill=64):
@@ -78,8 +80,9 @@ def main():
                          "shows the median and [min, max] ms/step")
     ap.add_argument("--kv-dtype", default="bf16",
                     help="--paged cache formats, comma-separated: bf16, fp8")
-    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
-                    help="fp8: one-byte weights, per-channel scales")
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+                    help="fp8: one-byte weights, per-channel scales; mxfp4: "
+                    "e2m1 nibbles, one e8m0 scale per 32")
     args = ap.parse_args()
     kv_dtypes = args.kv_dtype.split(",")
     assert set(kv_dtypes) <= {"bf16", "fp8"}, kv_dtypes
@@ -93,6 +96,9 @@ def main():
     if args.weight_dtype == "fp8":
         quantize_linears_fp8(model)
         print("# weights fp8 (e4m3, per-channel scales)")
+    elif args.weight_dtype == "mxfp4":
+        quantize_linears_mxfp4(model)
+        print("# weights mxfp4 (e2m1, one e8m0 scale per 32)")
 
     def timed(fn):
         ms = sorted(fn() / args.tokens * 1e3 for _ in range(args.reps))

@@ -1,17 +1,22 @@
-"""FP8 weight-only decode linear (csrc/hip/linear_w8.hip) against the best
-bf16 path for the same shape (ops.linear_sb: the GEMV kernel or hipBLASLt),
-alternated in one process, on the five Llama-3-8B decode shapes.
+"""FP8 and MXFP4 weight-only decode linears (csrc/hip/linear_w8.hip,
+csrc/hip/linear_w4.hip) against the best bf16 path for the same shape
+(ops.linear_sb: the GEMV kernel or hipBLASLt), alternated in one process, on
+the five Llama-3-8B decode shapes.
 
     python tools/linear_w8_bench.py [--rows 1,2,4,8,16,32] [--iters 50]
-                                    [--tiles 0]
+                                    [--tiles 0] [--w4 0:0]
 
 Each repetition times --iters back-to-back calls between two device
 events; a row shows the median of 7 repetitions with [min, max], in µs per
-call, and the weight-byte rate: N*K bytes for fp8, 2*N*K for bf16 (the
-bytes the algorithm must read; x, y and the scales are left out). The
+call, and the weight-byte rate: N*K bytes for fp8, 2*N*K for bf16 and
+N*K*17/32 for mxfp4 (the bytes the algorithm must read; x, y and the fp8
+scales are left out). An mxfp4 row also shows x-bytes per weight byte, the
+L2 traffic its tile costs: 4 * 16*ceil(M/16) / tile. The
 bound of this operation is bytes: at 8 TB/s of HBM the least time is
 weight bytes / 8e12. --tiles adds rows for a forced 16- or 32-channel
-block tile (0 is the shape rule of csrc/ops.hip).
+block tile (0 is the shape rule of csrc/ops.hip); --w4 adds mxfp4 rows for
+forced tile:split pairs, comma-separated (tile 64 or 128, split 1, 2, 4, 8;
+0:0 is the launcher's rule).
 
     python tools/linear_w8_bench.py --gemm [--rows 64,128,256,512,1024,2048]
                                     [--iters 20] [--split 0] [--rows-tile 0]
@@ -142,6 +147,7 @@ def main():
     ap.add_argument("--rows", default=None)
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--tiles", default="0")
+    ap.add_argument("--w4", default="0:0")
     ap.add_argument("--gemm", action="store_true")
     ap.add_argument("--split", default="0")
     ap.add_argument("--rows-tile", default="0")
@@ -158,12 +164,14 @@ def main():
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     tiles = [int(t) for t in args.tiles.split(",")]
+    w4s = [tuple(int(v) for v in p.split(":")) for p in args.w4.split(",")]
     print(f"{'shape':>8} {'N':>6} {'K':>5} {'M':>2}  path       "
           f"median µs [min, max]       TB/s  of 8 TB/s")
     with torch.no_grad():
         for name, N, K in SHAPES:
             w = torch.randn(N, K, device=dev, dtype=torch.bfloat16) * 0.02
             wq, scale = ops.quantize_weight_fp8(w)
+            w4, s4 = ops.quantize_weight_mxfp4(w)
             for M in [int(r) for r in args.rows.split(",")]:
                 x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
                 paths = [("bf16", 2 * N * K, lambda: ops.linear_sb(x, w))]
@@ -171,22 +179,35 @@ def main():
                     paths.append((
                         "fp8" if t == 0 else f"fp8 t{t}", N * K,
                         lambda t=t: ops._K.linear_w8(x, wq, scale, t)))
-                for _, _, fn in paths:  # warm up this shape on each path
+                for t, sp in w4s:
+                    tile = t or 128  # the launcher's default
+                    paths.append((
+                        "mxfp4" + (f" t{t}s{sp}" if t or sp else ""),
+                        N * K * 17 // 32,
+                        lambda t=t, sp=sp: ops._K.linear_w4(x, w4, s4, t, sp),
+                        4 * 16 * ((M + 15) // 16) / tile))
+                for _, _, fn, *_ in paths:  # warm up this shape on each path
                     timed(fn, 10)
                 times = [[] for _ in paths]
                 for _ in range(REPS):  # alternate the paths
-                    for ts, (_, _, fn) in zip(times, paths):
+                    for ts, (_, _, fn, *_) in zip(times, paths):
                         ts.append(timed(fn, args.iters))
-                for ts, (label, nbytes, _) in zip(times, paths):
+                for ts, (label, nbytes, _, *xr) in zip(times, paths):
                     ts.sort()
                     med = ts[REPS // 2]
                     rate = nbytes / (med * 1e-6)
                     print(f"{name:>8} {N:6d} {K:5d} {M:2d}  {label:<9}  "
                           f"{med:8.2f} [{ts[0]:8.2f}, {ts[-1]:8.2f}]  "
-                          f"{rate / 1e12:5.2f}  {100 * rate / HBM_PEAK:5.1f}%")
+                          f"{rate / 1e12:5.2f}  {100 * rate / HBM_PEAK:5.1f}%"
+                          + (f"  x/w {xr[0]:.2f}" if xr else ""))
                 fp8, bf = times[1], times[0]
                 print(f"{'':>8} fp8 slowest {'<' if fp8[-1] < bf[0] else '>='}"
                       f" bf16 fastest: {fp8[-1]:.2f} vs {bf[0]:.2f} µs")
+                for ts, (label, *_) in zip(times[len(tiles) + 1:],
+                                           paths[len(tiles) + 1:]):
+                    print(f"{'':>8} {label} slowest "
+                          f"{'<' if ts[-1] < fp8[0] else '>='} fp8 fastest: "
+                          f"{ts[-1]:.2f} vs {fp8[0]:.2f} µs")
 
 
 if __name__ == "__main__":
