@@ -24,6 +24,7 @@
 #include "hip/linear_w8.hip"
 #include "hip/linear_w8_gemm.hip"
 #include "hip/linear_w4.hip"
+#include "hip/linear_w4_gemm.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
@@ -592,6 +593,81 @@ at::Tensor linear_w8_gemm(at::Tensor x, at::Tensor wq, at::Tensor scale,
     if (bm == 64) { W8G_LAUNCH(64, false); } else { W8G_LAUNCH(128, false); }
   }
 #undef W8G_LAUNCH
+  return y;
+}
+
+// ---------------- MXFP4 weight-only GEMM (33+ rows) ----------------
+
+// The same product as linear_w4 for any number of rows, N % 128 == 0
+// (csrc/hip/linear_w4_gemm.hip). split: slices of K (0: the rule below);
+// rows_tile: 64 or 128 rows per block (0: the rule below). The overrides are
+// there for tools/linear_w8_bench.py and the tests. The result depends on
+// the split (the order of the fp32 sums), not on rows_tile.
+at::Tensor linear_w4_gemm(at::Tensor x, at::Tensor wq, at::Tensor scales,
+                          int64_t split, int64_t rows_tile) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16,
+              "linear_w4_gemm: x must be bf16");
+  TORCH_CHECK(x.dim() == 2, "linear_w4_gemm: x must be [M, K]");
+  long long N, K;
+  check_mxfp4(wq, scales, &N, &K, "linear_w4_gemm");
+  const long long M = x.size(0);
+  TORCH_CHECK(M >= 1 && M < (1ll << 22), "linear_w4_gemm: bad row count");
+  TORCH_CHECK(x.size(1) == K && K % 128 == 0,
+              "linear_w4_gemm: K must be a multiple of 128 and match x");
+  TORCH_CHECK(N % 128 == 0, "linear_w4_gemm: N must be a multiple of 128");
+  TORCH_CHECK(aligned16(x) && (uintptr_t)scales.data_ptr() % 4 == 0,
+              "linear_w4_gemm: x must be 16-byte and scales 4-byte aligned");
+  TORCH_CHECK(rows_tile == 0 || rows_tile == 64 || rows_tile == 128,
+              "linear_w4_gemm: rows_tile must be 0, 64 or 128");
+  TORCH_CHECK(split >= 0 && split <= 64, "linear_w4_gemm: split must be 0..64");
+  const long long cus =
+      at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  // Rows tile, from the forced comparison in PERFORMANCE.md: 64 rows while
+  // its tiles are at most one per CU and the weight (which it reads once
+  // per 64 rows, twice as often as the 128-row tile) is at most 2^25
+  // elements; 128 rows otherwise.
+  const long long tiles64 = (N / 128) * ((M + 63) / 64);
+  const int bm = rows_tile ? (int)rows_tile
+      : (M <= 64 || (tiles64 <= cus && N * K <= (1ll << 25)) ? 64 : 128);
+  const long long tiles = (N / 128) * ((M + bm - 1) / bm);
+  const long long steps = K / 128;
+  long long S = split;
+  if (S == 0) {
+    // As many blocks as fit the CUs at once (two a CU at 64 rows, one at
+    // 128: the LDS ring), at least 4 steps (512 k) a slice, and the fp32
+    // partials (4 bytes written and 4 read per element and slice) no more
+    // than the weight bytes: S*M*N*8 <= N*K/2.
+    S = std::min({(bm == 64 ? 2 : 1) * cus / tiles, steps / 4, K / (16 * M),
+                  16ll});
+  }
+  // a slice without steps would only store zeros
+  S = std::max(1ll, std::min(S, steps));
+  if (split > 0) S = split;  // forced: empty slices store zeros
+  auto y = at::empty({M, N}, x.options());
+  at::Tensor ws;
+  if (S > 1) ws = at::empty({S, M, N}, x.options().dtype(at::kFloat));
+  const dim3 grid((unsigned)(N / 128), (unsigned)((M + bm - 1) / bm),
+                  (unsigned)S);
+#define W4G_LAUNCH(BM, RING, SPLIT)                                          \
+  hipLaunchKernelGGL((linear_w4_gemm_kernel<BM, RING, SPLIT>), grid,         \
+                     dim3(256), 0, cur_stream(), (const short*)x.data_ptr(), \
+                     (const unsigned char*)wq.data_ptr(),                    \
+                     (const unsigned char*)scales.data_ptr(),                \
+                     (short*)y.data_ptr(),                                   \
+                     SPLIT ? ws.data_ptr<float>() : nullptr, (int)M, (int)N, \
+                     (int)K)
+  if (S > 1) {
+    if (bm == 64) { W4G_LAUNCH(64, 4, true); } else { W4G_LAUNCH(128, 3, true); }
+    hipLaunchKernelGGL(linear_w4_gemm_combine,
+                       dim3((unsigned)((M * N / 4 + 255) / 256)), dim3(256), 0,
+                       cur_stream(), ws.data_ptr<float>(),
+                       (short*)y.data_ptr(), M * N, (int)S);
+  } else {
+    if (bm == 64) { W4G_LAUNCH(64, 4, false); } else { W4G_LAUNCH(128, 3, false); }
+  }
+#undef W4G_LAUNCH
+  HIP_CHECK_KERNEL();
   return y;
 }
 
@@ -1362,6 +1438,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_w4", &linear_w4, py::arg("x"), py::arg("wq"),
         py::arg("scales"), py::arg("tile") = 0, py::arg("split") = 0);
   m.def("dequant_mxfp4", &dequant_mxfp4, py::arg("wq"), py::arg("scales"));
+  m.def("linear_w4_gemm", &linear_w4_gemm, py::arg("x"), py::arg("wq"),
+        py::arg("scales"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),

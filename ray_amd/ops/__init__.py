@@ -394,15 +394,50 @@ def linear_w4_ref(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor):
     return (x.double() @ w.t()).float()
 
 
+# (N, K) -> the largest row count that goes to linear_w4_gemm
+# (csrc/hip/linear_w4_gemm.hip) instead of dequant_mxfp4 + F.linear. The
+# rule is _W8_GEMM_TABLE's: a shape enters, with the largest M up to which it
+# won at every measured M (64, 96, 128, 256, 512, 1024, 2048), only if the
+# kernel's slowest repetition beat the fallback's fastest in
+# tools/linear_w8_bench.py --gemm --weights mxfp4 (times in the comments, µs
+# at the listed M, kernel median / fallback median). dequant_mxfp4 is a
+# cheap pass, so the limits end below 2048: beyond them, and for shapes not
+# listed, the fallback stays (PERFORMANCE.md has the losing rows).
+_W4_GEMM_TABLE: dict = {
+    # llama3-8b
+    (6144, 4096): 512,      # qkv:      36.6 /  51.4 (M = 64:  14.7 /  39.7)
+    (4096, 4096): 1024,     # o_proj:   38.5 /  50.9 (M = 64:  13.0 /  34.0)
+    (14336, 4096): 512,     # gate/up:  73.1 /  90.1 (M = 64:  27.1 /  64.1)
+    (4096, 14336): 256,     # down:     48.2 /  86.9 (M = 64:  28.1 /  74.6)
+    #                         (lost at 512: 112.8 / 116.5, slowest 113.4
+    #                         against the fallback's fastest 112.4)
+    (128256, 4096): 512,    # lm_head: 652.5 / 882.3 (M = 64: 127.9 / 576.9)
+    # llama3-1b
+    (3072, 2048): 1024,     # qkv:      21.3 /  31.4 (M = 64:  11.1 /  23.3)
+    (2048, 2048): 2048,     # o_proj:   22.6 /  29.7 (M = 64:  10.6 /  23.3)
+    (8192, 2048): 1024,     # gate/up:  42.8 /  48.8 (M = 64:  12.7 /  32.8)
+    (2048, 8192): 256,      # down:     30.9 /  39.4 (M = 64:  13.9 /  38.2)
+    #                         (lost at 512: 49.6 / 42.3)
+    (128256, 2048): 512,    # lm_head: 347.7 / 442.4 (M = 64:  63.2 / 298.8)
+}
+
+# test hook: send every qualifying call of 33+ rows to the kernel
+_W4_GEMM_FORCE = False
+
+
 def linear_w4(x: torch.Tensor, wq: torch.Tensor,
               scales: torch.Tensor) -> torch.Tensor:
     """x[..., K] · dequant(wq[N, K/2], scales[N, K/32])^T with MXFP4 weights
-    (see quantize_weight_mxfp4). bf16 GPU activations of 1 to 32 rows with
-    K % 128 == 0, grad off and contiguous, 16-byte-aligned operands run the
-    W4A16 skinny-GEMM kernel, which reads 17/32 byte per weight. More rows
-    on the GPU (prefill) dequantise with one kernel pass and call F.linear.
-    Everything else (CPU, other dtypes, odd K, grad on) dequantises in torch
-    to the activation dtype and calls F.linear."""
+    (see quantize_weight_mxfp4). bf16 GPU activations with K % 128 == 0,
+    grad off and contiguous, 16-byte-aligned operands run a kernel that
+    reads 17/32 byte per weight: the W4A16 skinny-GEMM kernel for 1 to 32
+    rows, and the W4A16 GEMM kernel (linear_w4_gemm: prefill chunks, decode
+    steps of more than 32 sequences) for 33 rows up to the limit
+    _W4_GEMM_TABLE lists for the shape (N, K), N % 128 == 0. More rows, and
+    shapes that are not listed, dequantise with one kernel pass and call
+    F.linear, which costs a bf16 copy of the weight per call. Everything
+    else (CPU, other dtypes, odd K, grad on) dequantises in torch to the
+    activation dtype and calls F.linear."""
     K = x.shape[-1]
     rows = x.numel() // K
     if (x.is_cuda and x.dtype == torch.bfloat16 and rows >= 1
@@ -410,9 +445,14 @@ def linear_w4(x: torch.Tensor, wq: torch.Tensor,
             and wq.is_contiguous() and scales.is_contiguous()
             and wq.data_ptr() % 16 == 0 and scales.data_ptr() % 4 == 0):
         _require_ext("linear_w4")
+        N = wq.shape[0]
+        gemm = (rows > 32 and N % 128 == 0 and
+                (_W4_GEMM_FORCE or rows <= _W4_GEMM_TABLE.get((N, K), 0)))
+        x2 = x.reshape(rows, K).contiguous() if gemm or rows <= 32 else None
+        if gemm and x2.data_ptr() % 16 == 0:
+            return _K.linear_w4_gemm(x2, wq, scales).view(*x.shape[:-1], N)
         if rows > 32:
             return torch.nn.functional.linear(x, _K.dequant_mxfp4(wq, scales))
-        x2 = x.reshape(rows, K).contiguous()
         if x2.data_ptr() % 16 == 0:
             y = _K.linear_w4(x2, wq, scales)
             return y.view(*x.shape[:-1], wq.shape[0])

@@ -21,6 +21,7 @@ forced tile:split pairs, comma-separated (tile 64 or 128, split 1, 2, 4, 8;
     python tools/linear_w8_bench.py --gemm [--rows 64,128,256,512,1024,2048]
                                     [--iters 20] [--split 0] [--rows-tile 0]
                                     [--models llama3-8b,llama3-1b]
+                                    [--weights fp8|mxfp4]
 
 --gemm measures the W8A16 GEMM for 33+ rows (csrc/hip/linear_w8_gemm.hip) on
 the projection shapes of --models, three paths alternated the same way:
@@ -30,7 +31,10 @@ yardstick; "gemm" is the kernel (--split and --rows-tile add rows for forced
 values, 0 is the launcher's rule); "bf16" is F.linear on a resident bf16
 weight, the price of not using fp8 at all, for information. All three are
 rated on N*K weight bytes. It ends with the peak extra memory of one lm_head
-call at 64 rows on the fallback and on the kernel.
+call at 64 rows on the fallback and on the kernel. --weights mxfp4 measures
+the W4A16 GEMM (csrc/hip/linear_w4_gemm.hip) the same way: the fallback is
+what ops.linear_w4 does for a shape that _W4_GEMM_TABLE does not list
+(ops._K.dequant_mxfp4, then F.linear), and the rate is on N*K*17/32 bytes.
 """
 import argparse
 import os
@@ -95,6 +99,10 @@ def fallback(x, wq, scale):
         x, (wq.float() * scale[:, None]).to(x.dtype))
 
 
+def fallback_w4(x, wq, scales):
+    return torch.nn.functional.linear(x, ops._K.dequant_mxfp4(wq, scales))
+
+
 def peak_extra(fn):
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -112,19 +120,25 @@ def main_gemm(args, dev):
           f"median µs [min, max]         TB/s  of 8 TB/s")
     for name, N, K in model_shapes(args.models.split(",")):
         w = torch.randn(N, K, device=dev, dtype=torch.bfloat16) * 0.02
-        wq, scale = ops.quantize_weight_fp8(w)
+        if args.weights == "mxfp4":
+            wq, scale = ops.quantize_weight_mxfp4(w)
+            fb_fn, kernel, nbytes = fallback_w4, ops._K.linear_w4_gemm, \
+                N * K * 17 // 32
+        else:
+            wq, scale = ops.quantize_weight_fp8(w)
+            fb_fn, kernel, nbytes = fallback, ops._K.linear_w8_gemm, N * K
         for M in rows:
             x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
-            paths = [("fallback", lambda: fallback(x, wq, scale))]
+            paths = [("fallback", lambda: fb_fn(x, wq, scale))]
             for sp, rt in forced:
                 label = "gemm" + (f" s{sp}" if sp else "") + (
                     f" r{rt}" if rt else "")
-                paths.append((label, lambda sp=sp, rt=rt: ops._K.linear_w8_gemm(
+                paths.append((label, lambda sp=sp, rt=rt: kernel(
                     x, wq, scale, sp, rt)))
             paths.append(("bf16", lambda: torch.nn.functional.linear(x, w)))
             times = alternate(paths, args.iters)
             for ts, (label, _) in zip(times, paths):
-                rate = N * K / (ts[REPS // 2] * 1e-6)
+                rate = nbytes / (ts[REPS // 2] * 1e-6)
                 print(f"{name:>10} {N:6d} {K:5d} {M:4d}  {label:<13}  "
                       f"{ts[REPS // 2]:9.2f} [{ts[0]:9.2f}, {ts[-1]:9.2f}]  "
                       f"{rate / 1e12:5.2f}  {100 * rate / HBM_PEAK:5.1f}%")
@@ -134,8 +148,8 @@ def main_gemm(args, dev):
                       f"fastest: {ts[-1]:.2f} vs {times[0][0]:.2f} µs")
         if name.endswith("lm_head"):
             x = torch.randn(64, K, device=dev, dtype=torch.bfloat16)
-            fb, _ = peak_extra(lambda: fallback(x, wq, scale))
-            kn, _ = peak_extra(lambda: ops._K.linear_w8_gemm(x, wq, scale))
+            fb, _ = peak_extra(lambda: fb_fn(x, wq, scale))
+            kn, _ = peak_extra(lambda: kernel(x, wq, scale))
             print(f"{name:>10} peak extra memory of one call at M = 64: "
                   f"fallback {fb:.1f} MiB, gemm {kn:.1f} MiB "
                   f"(y itself is {64 * N * 2 / 2 ** 20:.1f} MiB)")
@@ -152,6 +166,7 @@ def main():
     ap.add_argument("--split", default="0")
     ap.add_argument("--rows-tile", default="0")
     ap.add_argument("--models", default="llama3-8b,llama3-1b")
+    ap.add_argument("--weights", default="fp8", choices=["fp8", "mxfp4"])
     args = ap.parse_args()
     assert torch.cuda.is_available() and ops.HAVE_HIP_OPS, "needs the GPU"
     if args.gemm:
