@@ -25,6 +25,7 @@
 #include "hip/linear_w8_gemm.hip"
 #include "hip/linear_w4.hip"
 #include "hip/linear_w4_gemm.hip"
+#include "hip/lora.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/gemm_wgrad.hip"
@@ -671,9 +672,76 @@ at::Tensor linear_w4_gemm(at::Tensor x, at::Tensor wq, at::Tensor scales,
   return y;
 }
 
+// ---------------- batched per-row LoRA ----------------
+
+// y[m] += scale[s] * (x[m] · A[s]^T) · B[s]^T with s = idx[m], in place;
+// rows whose idx is -1 are left alone (csrc/hip/lora.hip). idx stays on the
+// device: the grids depend on the shapes only. split: slices of K in the
+// shrink kernel (0: the rule below); the result depends on it (the order of
+// the fp32 sums), so the override is for the tests and tools/lora_bench.py.
+at::Tensor lora_add(at::Tensor y, at::Tensor x, at::Tensor A, at::Tensor B,
+                    at::Tensor scale, at::Tensor idx, int64_t split) {
+  CHECK_IN(y); CHECK_IN(x); CHECK_IN(A); CHECK_IN(B); CHECK_IN(scale);
+  CHECK_IN(idx);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+                  y.scalar_type() == at::kBFloat16 &&
+                  A.scalar_type() == at::kBFloat16 &&
+                  B.scalar_type() == at::kBFloat16,
+              "lora_add: x, y, A and B must be bf16");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && idx.scalar_type() == at::kInt,
+              "lora_add: scale must be fp32 and idx int32");
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && A.dim() == 3 && B.dim() == 3 &&
+                  scale.dim() == 1 && idx.dim() == 1,
+              "lora_add: x [M,K], y [M,N], A [S,R,K], B [S,N,R], scale [S], "
+              "idx [M]");
+  const long long M = x.size(0), K = x.size(1), N = y.size(1);
+  const long long S = A.size(0), R = A.size(1);
+  TORCH_CHECK(M >= 1 && M < (1ll << 22), "lora_add: bad row count");
+  TORCH_CHECK(S >= 1 && S <= 64, "lora_add: 1 to 64 adapter slots");
+  TORCH_CHECK(R == 16 || R == 32 || R == 64, "lora_add: R must be 16, 32 or 64");
+  TORCH_CHECK(K % 128 == 0 && K > 0 && N % 128 == 0 && N > 0 &&
+                  N / 128 <= 65535,
+              "lora_add: K and N must be multiples of 128");
+  TORCH_CHECK(y.size(0) == M && idx.size(0) == M && A.size(2) == K &&
+                  B.size(0) == S && B.size(1) == N && B.size(2) == R &&
+                  scale.size(0) == S,
+              "lora_add: shapes do not match");
+  TORCH_CHECK(aligned16(x) && aligned16(y) && aligned16(A) && aligned16(B),
+              "lora_add: x, y, A and B must be 16-byte aligned");
+  TORCH_CHECK(split >= 0 && split <= 64, "lora_add: split must be 0..64");
+  // One 128-k step per wave and slice while K allows it: a listed row's
+  // work is latency, not bytes, so the slices are as short as the 8 waves
+  // can share. The partials (ks * R * 4 bytes a row) stay below the row of
+  // x they came from.
+  const long long steps = K / 128;
+  const long long ks =
+      split ? split : std::max(1ll, std::min(16ll, steps / 8));
+  // allocated here, as linear_w4_gemm's partials: safe under capture
+  auto ws = at::empty({ks, M, R}, x.options().dtype(at::kFloat));
+  const unsigned chunks = (unsigned)((M + 63) / 64);
+#define LORA_LAUNCH(RR)                                                      \
+  hipLaunchKernelGGL((lora_shrink_kernel<RR>),                               \
+                     dim3(chunks, (unsigned)ks, (unsigned)S), dim3(512), 0,  \
+                     cur_stream(), (const short*)x.data_ptr(),               \
+                     (const short*)A.data_ptr(), idx.data_ptr<int>(),        \
+                     ws.data_ptr<float>(), (int)M, (int)K);                  \
+  hipLaunchKernelGGL((lora_expand_kernel<RR>),                               \
+                     dim3(chunks, (unsigned)(N / 128), (unsigned)S),         \
+                     dim3(256), 0, cur_stream(), ws.data_ptr<float>(),       \
+                     (const short*)B.data_ptr(), scale.data_ptr<float>(),    \
+                     idx.data_ptr<int>(), (short*)y.data_ptr(), (int)M,      \
+                     (int)N, (int)ks)
+  if (R == 16) { LORA_LAUNCH(16); }
+  else if (R == 32) { LORA_LAUNCH(32); }
+  else { LORA_LAUNCH(64); }
+#undef LORA_LAUNCH
+  HIP_CHECK_KERNEL();
+  return y;
+}
+
 // ---------------- paged-KV decode attention ----------------
 
-#define CHECK_I32(x)                                                    \
+#define CHECK_I32(x)                                                   \
   CHECK_IN(x);                                                          \
   TORCH_CHECK(x.scalar_type() == at::kInt, #x " must be int32")
 
@@ -1440,6 +1508,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequant_mxfp4", &dequant_mxfp4, py::arg("wq"), py::arg("scales"));
   m.def("linear_w4_gemm", &linear_w4_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scales"), py::arg("split") = 0, py::arg("rows_tile") = 0);
+  m.def("lora_add", &lora_add, py::arg("y"), py::arg("x"), py::arg("A"),
+        py::arg("B"), py::arg("scale"), py::arg("idx"), py::arg("split") = 0);
   m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),

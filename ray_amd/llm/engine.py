@@ -21,6 +21,7 @@ from ray_amd.models.llama import (
     GraphedDecoder,
     KVCache,
     LlamaModel,
+    add_lora_slots,
     quantize_linears_fp8,
     quantize_linears_mxfp4,
 )
@@ -61,6 +62,16 @@ class LLMConfig:
     # byte per weight (ops.LinearW4), read by the W4A16 skinny-GEMM kernel.
     # Activations stay in the model dtype.
     weight_dtype: str = "auto"
+    # ContinuousBatchingEngine with kv_cache="paged" only. max_loras > 0
+    # gives every decoder-layer projection that many LoRA adapter slots of
+    # rank max_lora_rank (rounded up to 16, 32 or 64; adapters of smaller
+    # rank are stored zero-padded). add_lora(name, tensors) fills a slot,
+    # submit(..., lora=name) runs a request with it, and requests with
+    # different adapters, or none, decode in the same batch: the adapters'
+    # part is two HIP kernels per projection that read each row's slot from
+    # device memory (ops.lora_add), over bf16, fp8 or MXFP4 base weights.
+    max_loras: int = 0
+    max_lora_rank: int = 16
     # Sampling defaults of a request (each can be given per request).
     # top_k: keep the k largest logits, ties at the k-th kept (0: off).
     # top_p: then keep the smallest set of largest logits whose mass reaches
@@ -138,6 +149,20 @@ _KV_CACHE_DTYPES = {
 _WEIGHT_DTYPES = ("auto", "bf16", "fp8", "fp8_e4m3", "mxfp4")
 
 
+def _lora_rank(config: LLMConfig) -> int:
+    """0 without adapter slots, else max_lora_rank rounded up to a rank
+    the kernels have."""
+    if config.max_loras < 0 or config.max_loras > 64:
+        raise ValueError("max_loras must be 0..64")
+    if config.max_loras == 0:
+        return 0
+    for r in ops.LORA_RANKS:
+        if 1 <= config.max_lora_rank <= r:
+            return r
+    raise ValueError(f"max_lora_rank must be 1..{ops.LORA_RANKS[-1]}, got "
+                     f"{config.max_lora_rank!r}")
+
+
 def _quantized_weights(config: LLMConfig):
     """None for model-dtype weights, else "fp8" or "mxfp4"."""
     if config.weight_dtype not in _WEIGHT_DTYPES:
@@ -157,6 +182,9 @@ class LLMEngine(_Sampling):
         if wq:
             raise ValueError(f"weight_dtype='{wq}' needs "
                              "ContinuousBatchingEngine with kv_cache='paged'")
+        if _lora_rank(config):
+            raise ValueError("max_loras needs ContinuousBatchingEngine "
+                             "with kv_cache='paged'")
         cfg = CONFIGS[config.model_id]
         self.model_cfg = cfg
         self.device = (
@@ -309,6 +337,14 @@ class ContinuousBatchingEngine(_Sampling):
                 quantize_linears_fp8(self.model)
             else:
                 quantize_linears_mxfp4(self.model)
+        self._lora_rank = _lora_rank(config)
+        # name -> {"slot": adapter slot, "root": its prefix-cache root}
+        self._loras: dict = {}
+        self._lora_roots = 0
+        if self._lora_rank:
+            if not self._paged:
+                raise ValueError("max_loras needs kv_cache='paged'")
+            add_lora_slots(self.model, config.max_loras, self._lora_rank)
         if self._paged:
             from ray_amd.llm.paged import PagedDecoder
 
@@ -348,6 +384,8 @@ class ContinuousBatchingEngine(_Sampling):
                                        device=self.device)
         self.stats = {"requests": 0, "tokens_generated": 0,
                       "decode_steps": 0}
+        if self._lora_rank:
+            self.stats["loras_loaded"] = 0
         self.stats["weight_bytes"] = sum(
             t.numel() * t.element_size()
             for t in (*self.model.parameters(), *self.model.buffers()))
@@ -368,11 +406,80 @@ class ContinuousBatchingEngine(_Sampling):
         """KV rows a request can ever occupy (prompt + decode budget)."""
         return min(prompt_len + max_new_tokens, self.max_T)
 
+    def _lora_modules(self) -> dict:
+        return {name: mod for name, mod in self.model.named_modules()
+                if isinstance(mod, ops.LoraLinear)}
+
+    def add_lora(self, name: str, tensors: dict,
+                 alpha: Optional[float] = None):
+        """Load an adapter into a free slot. `tensors` maps the path of a
+        decoder-layer projection ("layers.3.attn.o_proj") to (A [r, K],
+        B [N, r]); projections that are not named keep a zero adapter. The
+        adapter's part of a projection is scale * (x A^T) B^T with scale =
+        alpha / r, or 1 when alpha is None. The slot's buffers are written
+        in place, so a captured decode graph stays valid."""
+        if not self._lora_rank:
+            raise ValueError("add_lora needs LLMConfig.max_loras > 0")
+        if name in self._loras:
+            raise ValueError(f"adapter {name!r} is already loaded")
+        used = {v["slot"] for v in self._loras.values()}
+        free = [s for s in range(self.config.max_loras) if s not in used]
+        if not free:
+            raise ValueError(
+                f"all {self.config.max_loras} adapter slots are in use")
+        mods = self._lora_modules()
+        for path, (A, B) in tensors.items():
+            mod = mods.get(path)
+            if mod is None:
+                raise ValueError(f"{path!r} is not an adapted projection")
+            r = A.shape[0] if A.dim() == 2 else -1
+            if not 1 <= r <= self._lora_rank:
+                raise ValueError(
+                    f"{path}: rank {r} is not in 1..{self._lora_rank}")
+            if (tuple(A.shape) != (r, mod.in_features)
+                    or tuple(B.shape) != (mod.out_features, r)):
+                raise ValueError(
+                    f"{path}: A must be [r, {mod.in_features}] and B "
+                    f"[{mod.out_features}, r], got {tuple(A.shape)} and "
+                    f"{tuple(B.shape)}")
+        slot = free[0]
+        with torch.no_grad():
+            for path, mod in mods.items():
+                mod.lora_A[slot].zero_()
+                mod.lora_B[slot].zero_()
+                mod.lora_scale[slot] = 0.0
+                if path in tensors:
+                    A, B = tensors[path]
+                    r = A.shape[0]
+                    mod.lora_A[slot, :r].copy_(A)
+                    mod.lora_B[slot, :, :r].copy_(B)
+                    mod.lora_scale[slot] = (1.0 if alpha is None
+                                            else float(alpha) / r)
+        # a root of its own per call: neither the base model nor an earlier
+        # adapter of the same name can hit this one's cached pages
+        self._lora_roots -= 1
+        self._loras[name] = {"slot": slot, "root": self._lora_roots}
+        self.stats["loras_loaded"] = len(self._loras)
+
+    def remove_lora(self, name: str):
+        """Free the adapter's slot; not while a request uses it."""
+        if name not in self._loras:
+            raise ValueError(f"unknown adapter {name!r}")
+        for r in (*self._queue, *self._slots):
+            if r is not None and r["lora"] == name:
+                raise ValueError(
+                    f"adapter {name!r} is used by request {r['id']}")
+        del self._loras[name]
+        self.stats["loras_loaded"] = len(self._loras)
+
     def submit(self, prompt_ids: List[int], max_new_tokens: int = 32,
                temperature: Optional[float] = None,
                top_k: Optional[int] = None, top_p: Optional[float] = None,
-               seed: Optional[int] = None) -> int:
+               seed: Optional[int] = None,
+               lora: Optional[str] = None) -> int:
         sampling = self._request_sampling(temperature, top_k, top_p, seed)
+        if lora is not None and lora not in self._loras:
+            raise ValueError(f"unknown adapter {lora!r}")
         rid = self._next_id
         self._next_id += 1
         cfg = self.model_cfg
@@ -390,7 +497,7 @@ class ContinuousBatchingEngine(_Sampling):
                     f"{self.decoder.pool.num_usable}; raise kv_num_pages")
         self._queue.append({
             "id": rid, "prompt": prompt,
-            "max_new_tokens": max_new_tokens,
+            "max_new_tokens": max_new_tokens, "lora": lora,
             **sampling,
         })
         self.stats["requests"] += 1
@@ -417,7 +524,12 @@ class ContinuousBatchingEngine(_Sampling):
             req = self._queue.pop(0)
             toks = torch.tensor(req["prompt"], device=self.device)
             with torch.no_grad():
-                if self._paged:
+                if self._paged and req["lora"] is not None:
+                    ad = self._loras[req["lora"]]
+                    logits = self.decoder.prefill_slot(
+                        slot, toks, reserve, lora_slot=ad["slot"],
+                        prefix_root=ad["root"])
+                elif self._paged:
                     logits = self.decoder.prefill_slot(slot, toks, reserve)
                 else:
                     logits = self.decoder.prefill_slot(slot, toks)

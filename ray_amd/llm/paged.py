@@ -32,8 +32,10 @@ class PagedKVPool:
     sequence. It is never handed out.
 
     Prefix index: a full prompt page is keyed by (parent, its page_size
-    token ids), where parent is the node id of the page before it (0 at
-    the root). Node ids are never reused, so an entry whose ancestor was
+    token ids), where parent is the node id of the page before it (at
+    the root, the `root` given to match_prefix / register_prefix: 0 for
+    the base model, a negative number of its own for each loaded adapter,
+    whose K/V differ). Node ids are never reused, so an entry whose ancestor was
     evicted can no longer be reached. One page id addresses every
     layer's tensors, so the index is per pool. An indexed page whose
     count drops to 0 keeps its contents and waits in an LRU; alloc takes
@@ -152,12 +154,13 @@ class PagedKVPool:
         ps = self.page_size
         return tuple(int(t) for t in tokens[i * ps:(i + 1) * ps])
 
-    def match_prefix(self, tokens, max_pages: int) -> List[int]:
-        """Longest run of indexed full pages that spell the start of
-        `tokens`, at most max_pages long, with a reference taken on
-        each."""
+    def match_prefix(self, tokens, max_pages: int,
+                     root: int = 0) -> List[int]:
+        """Longest run of indexed full pages under `root` that spell the
+        start of `tokens`, at most max_pages long, with a reference taken
+        on each."""
         pages: List[int] = []
-        parent = 0
+        parent = root
         for i in range(min(max_pages, len(tokens) // self.page_size)):
             p = self._index.get((parent, self._page_tokens(tokens, i)))
             if p is None:
@@ -171,11 +174,11 @@ class PagedKVPool:
             parent = self._node[p]
         return pages
 
-    def register_prefix(self, tokens, pages: List[int]):
-        """Index every full page of the prompt `tokens`, held in
-        `pages` (allocated, in order), that is not indexed yet. A key
+    def register_prefix(self, tokens, pages: List[int], root: int = 0):
+        """Index under `root` every full page of the prompt `tokens`, held
+        in `pages` (allocated, in order), that is not indexed yet. A key
         that is already present keeps its first page."""
-        parent = 0
+        parent = root
         for i in range(min(len(pages), len(tokens) // self.page_size)):
             key = (parent, self._page_tokens(tokens, i))
             p = self._index.get(key)
@@ -226,7 +229,9 @@ class PagedDecoder:
     release_slot and capture. All per-step state (tokens, positions,
     lengths, block table, split workspace) is in static device buffers
     read by the kernels, so one captured graph replays for any mix of
-    sequence lengths."""
+    sequence lengths. That includes the adapters of a model wrapped by
+    add_lora_slots (wrap before building the decoder): the step reads
+    each slot's adapter from the static buffer slot_lora."""
 
     def __init__(self, model, batch_size: int, max_T: int, device,
                  num_pages: Optional[int] = None,
@@ -263,6 +268,11 @@ class PagedDecoder:
         self.in_tok = torch.zeros(batch_size, 1, dtype=torch.long,
                                   device=device)
         self._slot_pages: List[List[int]] = [[] for _ in range(batch_size)]
+        # slot -> adapter slot of the model's LoraLinear modules, -1: none
+        self.lora_state = getattr(model, "lora_state", None)
+        self.slot_lora = torch.full((batch_size,), -1, dtype=torch.int32,
+                                    device=device)
+        self._slot_lora: List[int] = [-1] * batch_size
         # fixed at construction: a captured graph bakes the grid in
         self.num_splits = ops.default_num_splits(
             batch_size, cfg.num_kv_heads, max_T, device)
@@ -291,6 +301,22 @@ class PagedDecoder:
         self.block_table[slot].zero_()
         self.seq_lens[slot] = 0
         self.pos[slot] = -1
+        self._set_slot_lora(slot, -1)
+
+    def _set_slot_lora(self, slot: int, lora_slot: int):
+        if lora_slot != -1 and self.lora_state is None:
+            raise ValueError("lora_slot needs a model wrapped by "
+                             "add_lora_slots")
+        if self._slot_lora[slot] != lora_slot:
+            self._slot_lora[slot] = lora_slot
+            self.slot_lora[slot] = lora_slot
+
+    def _row_lora(self, slot: int, T: int):
+        """state.idx of a prefill of T rows of `slot`: None for the base."""
+        if self._slot_lora[slot] < 0:
+            return None
+        return torch.full((T,), self._slot_lora[slot], dtype=torch.int32,
+                          device=self.device)
 
     def set_slot_len(self, slot: int, length: int):
         self.seq_lens[slot] = length
@@ -313,11 +339,14 @@ class PagedDecoder:
         return pages
 
     def prefill_slot(self, slot: int, toks: torch.Tensor,
-                     reserve_tokens: Optional[int] = None):
+                     reserve_tokens: Optional[int] = None,
+                     lora_slot: int = -1, prefix_root: int = 0):
         """Run the prompt through the model's normal prefill, scattering
         its K/V into freshly allocated pages. Pages for `reserve_tokens`
         (prompt + decode budget; default max_T) are taken up front.
-        Returns last-position logits [V]."""
+        `lora_slot` is the adapter the sequence runs with until the slot is
+        released (-1: the base model) and `prefix_root` the root its cached
+        pages hang from (PagedKVPool). Returns last-position logits [V]."""
         n = toks.numel()
         if reserve_tokens is None:
             reserve_tokens = self.max_T
@@ -331,22 +360,32 @@ class PagedDecoder:
         if (self.prefix_caching or self.prefill_chunk is not None
                 or self.pool.is_fp8):
             return self._prefill_slot_paged(slot, toks,
-                                            max(reserve_tokens, n))
+                                            max(reserve_tokens, n),
+                                            lora_slot, prefix_root)
         self.prefill_tokens_computed += n
         pages = self.reserve_slot(slot, max(reserve_tokens, n))
+        self._set_slot_lora(slot, lora_slot)
         page_ids = torch.tensor(pages, dtype=torch.long, device=self.device)
         caches = [
             _PagedSlotCache(self.pool.k[li], self.pool.v[li], page_ids,
                             self.pool.page_size)
             for li in range(self.m.cfg.num_layers)
         ]
-        logits = self.m(toks.view(1, -1), kv_caches=caches, pos0=0)[0, -1]
+        if self.lora_state is not None:
+            self.lora_state.idx = self._row_lora(slot, n)
+        try:
+            logits = self.m(toks.view(1, -1), kv_caches=caches,
+                            pos0=0)[0, -1]
+        finally:
+            if self.lora_state is not None:
+                self.lora_state.idx = None
         self.set_slot_len(slot, n)
         return logits
 
     @torch.no_grad()
     def _prefill_slot_paged(self, slot: int, toks: torch.Tensor,
-                            reserve_tokens: int):
+                            reserve_tokens: int, lora_slot: int = -1,
+                            prefix_root: int = 0):
         """Prefill through the paged prefill kernel: reuse the cached
         pages that spell the start of the prompt, then run the rest in
         chunks that attend to the pages directly.
@@ -359,13 +398,15 @@ class PagedDecoder:
             raise ValueError("prefill of an empty prompt")
         ps = self.pool.page_size
         self.release_slot(slot)
+        self._set_slot_lora(slot, lora_slot)
         need = pages_for(min(reserve_tokens, self.max_T))
         tok_list = toks.tolist()
         shared: List[int] = []
         if self.prefix_caching:
             # at most (n-1)//ps pages: at least one token is computed,
             # so there are last-position logits
-            shared = self.pool.match_prefix(tok_list, (n - 1) // ps)
+            shared = self.pool.match_prefix(tok_list, (n - 1) // ps,
+                                            prefix_root)
         fresh = self.pool.alloc(need - len(shared))
         if fresh is None:
             self.pool.free(shared[::-1])
@@ -388,7 +429,8 @@ class PagedDecoder:
         self.prefix_hit_tokens += ctx
         self.prefill_tokens_computed += n - ctx
         if self.prefix_caching:
-            self.pool.register_prefix(tok_list, pages[: n // ps])
+            self.pool.register_prefix(tok_list, pages[: n // ps],
+                                      prefix_root)
         self.set_slot_len(slot, n)
         return logits
 
@@ -398,6 +440,16 @@ class PagedDecoder:
         append their rotated K and raw V to the slot's pages, then
         attend to the pages (append-then-attend, as the decode step).
         Returns last-position logits [V] when `last`, else None."""
+        if self.lora_state is not None:
+            self.lora_state.idx = self._row_lora(slot, toks.numel())
+        try:
+            return self._prefill_chunk_rows(slot, toks, pos0, last)
+        finally:
+            if self.lora_state is not None:
+                self.lora_state.idx = None
+
+    def _prefill_chunk_rows(self, slot: int, toks: torch.Tensor, pos0: int,
+                            last: bool):
         m = self.m
         T = toks.numel()
         ps = self.pool.page_size
@@ -440,6 +492,16 @@ class PagedDecoder:
     # ---- decode -----------------------------------------------------
 
     def _step(self):
+        if self.lora_state is None:
+            return self._step_rows()
+        # a static buffer: captured once, any mix of adapters replays
+        self.lora_state.idx = self.slot_lora
+        try:
+            return self._step_rows()
+        finally:
+            self.lora_state.idx = None
+
+    def _step_rows(self):
         m = self.m
         B = self.B
         x = m.embed(self.in_tok)  # [B,1,H]

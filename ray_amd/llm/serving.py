@@ -40,11 +40,11 @@ class LLMServer:
         self._pump_task = None
 
     async def _generate_cb(self, prompt_ids, max_new_tokens, temperature,
-                           top_k, top_p, seed):
+                           top_k, top_p, seed, lora=None):
         import asyncio
 
         rid = self.engine.submit(prompt_ids, max_new_tokens, temperature,
-                                 top_k, top_p, seed)
+                                 top_k, top_p, seed, lora)
         fut = asyncio.get_running_loop().create_future()
         self._futures[rid] = fut
         if self._pump_task is None or self._pump_task.done():
@@ -56,11 +56,15 @@ class LLMServer:
                        temperature: float = 0.0,
                        top_k: Optional[int] = None,
                        top_p: Optional[float] = None,
-                       seed: Optional[int] = None):
+                       seed: Optional[int] = None,
+                       lora: Optional[str] = None):
         if self._batching == "continuous":
             return await self._generate_cb(
-                prompt_ids, max_new_tokens, temperature, top_k, top_p, seed
+                prompt_ids, max_new_tokens, temperature, top_k, top_p, seed,
+                lora
             )
+        if lora is not None:
+            raise ValueError("lora needs batching='continuous'")
         return self.engine.generate(prompt_ids, max_new_tokens, temperature,
                                     top_k, top_p, seed)
 
@@ -79,6 +83,7 @@ class LLMServer:
             None if body.get("top_k") is None else int(body["top_k"]),
             None if body.get("top_p") is None else float(body["top_p"]),
             None if body.get("seed") is None else int(body["seed"]),
+            body.get("lora"),
         )
         return {
             "id": "cmpl-ray-amd",

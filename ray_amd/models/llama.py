@@ -54,11 +54,18 @@ CONFIGS = {
 _QUANT_LINEARS = (ops.LinearW8, ops.LinearW4)
 
 
+# projections the fused training paths do not take: no plain `.weight`
+_WRAPPED_LINEARS = _QUANT_LINEARS + (ops.LoraLinear,)
+
+
 def proj(mod, x, lin=None):
     """The projection `mod` applied to x. `lin(x, weight)` overrides the
     matmul of a bf16 Linear (decode paths pass the GEMV fast path); an
     ops.LinearW8 or ops.LinearW4 always runs its own quantised-weight
-    linear."""
+    linear. An ops.LoraLinear sends its base through the same rule and
+    then adds its adapters' part."""
+    if isinstance(mod, ops.LoraLinear):
+        return mod.add(proj(mod.base, x, lin), x)
     if lin is None or isinstance(mod, _QUANT_LINEARS):
         return mod(x)
     return lin(x, mod.weight)
@@ -92,6 +99,32 @@ def _quantize_linears(model, cls):
         swap(layer.mlp, ("gate_proj", "up_proj", "down_proj"))
     swap(model, ("lm_head",))
     return model
+
+
+_LORA_TARGETS = {
+    "attn": ("qkv_proj", "q_proj", "k_proj", "v_proj", "o_proj"),
+    "mlp": ("gate_proj", "up_proj", "down_proj"),
+}
+
+
+def add_lora_slots(model: "LlamaModel", max_loras: int,
+                   rank: int) -> "ops.LoraState":
+    """Wrap, in place, every decoder-layer projection (not lm_head) in an
+    ops.LoraLinear with `max_loras` empty adapter slots of rank `rank`
+    (16, 32 or 64). Returns the state the wrappers share, also kept as
+    model.lora_state: set its `idx` to the int32 row -> slot tensor of a
+    call (-1: no adapter) to apply the adapters, None to run the base alone. The model then serves inference
+    only. Quantise first (quantize_linears_*), then add the slots."""
+    state = ops.LoraState()
+    for layer in model.layers:
+        for part, names in _LORA_TARGETS.items():
+            parent = getattr(layer, part)
+            for name in names:
+                if hasattr(parent, name):
+                    setattr(parent, name, ops.LoraLinear(
+                        getattr(parent, name), max_loras, rank, state))
+    model.lora_state = state
+    return state
 
 
 class Attention(nn.Module):
@@ -156,7 +189,7 @@ class Attention(nn.Module):
 
         if (flash(x) and self._fused_qkv and T % 256 == 0 and pos0 == 0
                 and ops._FUSED_QKV_ATTN
-                and not isinstance(self.qkv_proj, _QUANT_LINEARS)
+                and not isinstance(self.qkv_proj, _WRAPPED_LINEARS)
                 and self.qkv_proj.weight.dtype == torch.bfloat16):
             # RoPE in place on the projection output, attention on its
             # q/k/v column sections, one packed gradient in backward
@@ -202,7 +235,7 @@ class MLP(nn.Module):
         )
 
     def forward(self, x):
-        if isinstance(self.gate_proj, _QUANT_LINEARS):
+        if isinstance(self.gate_proj, _WRAPPED_LINEARS):
             return self.down_proj(
                 ops.swiglu(self.gate_proj(x), self.up_proj(x)))
         gate, up = ops.swiglu_mlp_in(

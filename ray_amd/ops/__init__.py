@@ -610,6 +610,108 @@ class Linear(torch.nn.Linear):
         return linear(x, self.weight, self.bias)
 
 
+# --------------------------------------------------------------------------
+# Batched per-row LoRA (csrc/hip/lora.hip)
+# --------------------------------------------------------------------------
+
+LORA_RANKS = (16, 32, 64)
+
+
+def lora_ref(y, x, A, B, scale, idx, dtype=torch.float64):
+    """The rule, out of place: row m of the result is
+    y[m] + scale[s] * (x[m] @ A[s].T) @ B[s].T with s = idx[m], and y[m]
+    itself where idx[m] is -1 (such a row's x is not read). y [M, N],
+    x [M, K], A [S, R, K], B [S, N, R], scale [S], idx [M] integers. The
+    products are taken in `dtype`, which is also the result's."""
+    out = y.to(dtype).clone()
+    for s in idx.unique().tolist():
+        if s < 0:
+            continue
+        rows = (idx == s).nonzero().flatten()
+        h = x.index_select(0, rows).to(dtype) @ A[s].to(dtype).t()
+        out.index_add_(0, rows,
+                       (h @ B[s].to(dtype).t()) * scale[s].to(dtype))
+    return out
+
+
+def lora_add(y, x, A, B, scale, idx, split: int = 0):
+    """y[m] += scale[s] * (x[m] @ A[s].T) @ B[s].T with s = idx[m], in
+    place; returns y. bf16 GPU operands with grad off, R in LORA_RANKS,
+    K % 128 == 0 and N % 128 == 0 run the two HIP kernels, which read idx on
+    the device (`split` forces their number of K slices). Everything else
+    (CPU, other dtypes or shapes) computes lora_ref in fp32 (fp64 for fp64
+    operands) and copies it into y."""
+    M, K = x.shape
+    N, R = B.shape[1], B.shape[2]
+    if (x.is_cuda and x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16
+            and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16
+            and not torch.is_grad_enabled() and R in LORA_RANKS
+            and K % 128 == 0 and N % 128 == 0 and 1 <= M < 2 ** 22
+            and x.is_contiguous() and y.is_contiguous()
+            and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0):
+        _require_ext("lora_add")
+        return _K.lora_add(y, x, A, B, scale, idx.int(), split)
+    wide = torch.float64 if x.dtype == torch.float64 else torch.float32
+    y.copy_(lora_ref(y, x, A, B, scale, idx, wide))
+    return y
+
+
+class LoraState:
+    """What the LoraLinear modules of one model share: `idx`, the int32
+    row -> adapter slot tensor of the current call (-1: no adapter), or
+    None while no adapter is in play."""
+
+    def __init__(self):
+        self.idx = None
+
+
+class LoraLinear(torch.nn.Module):
+    """A projection (ops.Linear, LinearW8 or LinearW4) with `max_loras`
+    adapter slots of rank `rank` on top: buffers lora_A [S, R, K], lora_B
+    [S, N, R] and lora_scale [S], all zero until an adapter is copied in.
+    forward is the base's, plus lora_add on the flattened rows while
+    state.idx is set."""
+
+    def __init__(self, base: torch.nn.Module, max_loras: int, rank: int,
+                 state: "LoraState" = None):
+        super().__init__()
+        if rank not in LORA_RANKS:
+            raise ValueError(f"LoRA rank must be one of {LORA_RANKS}")
+        if not 1 <= max_loras <= 64:
+            raise ValueError("max_loras must be 1..64")
+        self.base = base
+        self.in_features, self.out_features = (base.in_features,
+                                               base.out_features)
+        self.state = state if state is not None else LoraState()
+        ref = next(iter((*base.parameters(), *base.buffers())))
+        dtype = (ref.dtype if ref.dtype.is_floating_point
+                 and ref.element_size() > 1 else torch.bfloat16)
+        kw = {"device": ref.device, "dtype": dtype}
+        self.register_buffer("lora_A", torch.zeros(
+            max_loras, rank, self.in_features, **kw))
+        self.register_buffer("lora_B", torch.zeros(
+            max_loras, self.out_features, rank, **kw))
+        self.register_buffer("lora_scale", torch.zeros(
+            max_loras, device=ref.device, dtype=torch.float32))
+
+    def add(self, y, x):
+        """The adapters' part, added in place to y = base(x)."""
+        idx = self.state.idx
+        if idx is None:
+            return y
+        y2 = y.reshape(-1, self.out_features)
+        x2 = x.reshape(-1, self.in_features)
+        if not y2.is_contiguous() or y2.data_ptr() != y.data_ptr():
+            raise ValueError("LoraLinear: the base's output must be "
+                             "contiguous")
+        lora_add(y2, x2.contiguous(), self.lora_A, self.lora_B,
+                 self.lora_scale, idx)
+        return y
+
+    def forward(self, x):
+        return self.add(self.base(x), x)
+
+
 class _SwigluMlpIn(torch.autograd.Function):
     """gate = x W_gate^T, up = x W_up^T. Backward: one grouped weight
     gradient launch (both share x). dx is the sum of the two dgrad GEMMs,
