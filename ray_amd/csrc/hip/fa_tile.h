@@ -1,7 +1,7 @@
 // Tile math shared by the attention kernels: fragment types, the two
 // cvt_pk forms, the K swizzle, S' = K·Q^T, the online-softmax step and
-// P·V. flash_attn_v5.hip and paged_attn_prefill.hip call s_tile,
-// softmax_step and pv_tile; flash_attn_v7.hip calls the two-phase form of
+// P·V. flash_attn_v5.hip, paged_attn_prefill.hip and paged_attn_verify.hip
+// call s_tile, softmax_step and pv_tile; flash_attn_v7.hip calls the two-phase form of
 // the same arithmetic at the end of this file. The backward kernels take
 // the types and conversions and the pieces that are the same in either
 // direction: c_row, the packed exchange of a C-layout tile (pack_swap),

@@ -28,6 +28,7 @@
 #include "hip/lora.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
+#include "hip/paged_attn_verify.hip"
 #include "hip/gemm_wgrad.hip"
 #include "hip/sample.hip"
 
@@ -1057,6 +1058,158 @@ void kv_append_paged(at::Tensor k, at::Tensor v, int64_t pos0,
 #undef KA_LAUNCH
 }
 
+// ---------------- paged-KV verify attention (speculative decoding) --------
+
+// q [B, Tq, Hq, D] at positions ctx_lens[b] .. ctx_lens[b]+Tq-1 whose own
+// K/V are already appended, Tq * (Hq/Hkv) <= PV_MAX_ROWS. num_splits > 1
+// goes through a workspace of B*Tq*Hq*num_splits*(D+2) fp32 elements
+// (o partials, then (m, l) pairs: paged_attn_decode's layout with Tq*Hq
+// heads) and the same reduce kernel.
+at::Tensor paged_attn_verify(at::Tensor q, at::Tensor k_cache,
+                             at::Tensor v_cache, at::Tensor block_table,
+                             at::Tensor ctx_lens, at::Tensor q_lens,
+                             int64_t num_splits,
+                             c10::optional<at::Tensor> workspace,
+                             double k_scale, double v_scale) {
+  CHECK_IN(q);
+  CHECK_I32(block_table);
+  CHECK_I32(ctx_lens);
+  CHECK_I32(q_lens);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "q must be bf16");
+  TORCH_CHECK(q.dim() == 4, "q must be [B, Tq, Hq, D]");
+  TORCH_CHECK(aligned16(q), "paged_attn_verify: q must be 16-byte aligned");
+  int B = (int)q.size(0), Hq = (int)q.size(2), D = (int)q.size(3);
+  int Hkv;
+  const bool fp8 = check_paged_attn(k_cache, v_cache, block_table, B, Hq, D,
+                                    k_scale, v_scale, &Hkv);
+  TORCH_CHECK(fp8 || (aligned16(k_cache) && aligned16(v_cache)),
+              "paged_attn_verify: caches must be 16-byte aligned");
+  TORCH_CHECK(block_table.size(1) <= (1 << 26),
+              "paged_attn_verify: block table too wide");
+  TORCH_CHECK(ctx_lens.dim() == 1 && ctx_lens.size(0) == B &&
+              q_lens.dim() == 1 && q_lens.size(0) == B,
+              "ctx_lens and q_lens must be [B]");
+  const int rep = Hq / Hkv;
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) * rep <= PV_MAX_ROWS,
+              "paged_attn_verify: Tq * (Hq/Hkv) must be 1..", PV_MAX_ROWS,
+              ", got Tq ", q.size(1), " at Hq/Hkv ", rep);
+  int Tq = (int)q.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && Hkv <= 65535,
+              "paged_attn_verify: B and Hkv must fit a grid dimension");
+  int S = (int)num_splits;
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 1024,
+              "paged_attn_verify: num_splits must be 1..1024");
+  auto out = at::empty_like(q);
+  at::Tensor ws;
+  float *ws_o = nullptr, *ws_ml = nullptr;
+  if (S > 1) {
+    long long need = (long long)B * Tq * Hq * S * (D + 2);
+    if (workspace.has_value()) {
+      ws = *workspace;
+      CHECK_IN(ws);
+      TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= need &&
+                  aligned16(ws),
+                  "paged_attn_verify: workspace must be fp32, 16-byte "
+                  "aligned, with >= B*Tq*Hq*S*(D+2) elements");
+    } else {
+      ws = at::empty({need}, q.options().dtype(at::kFloat));
+    }
+    ws_o = ws.data_ptr<float>();
+    ws_ml = ws_o + (long long)B * Tq * Hq * S * D;
+  }
+  const int rep_shift = rep == 1 ? 0 : rep == 2 ? 1 : rep == 4 ? 2 : 3;
+#define PV_LAUNCH_T(DD, FP8)                                                \
+  hipLaunchKernelGGL((paged_attn_verify_kernel<DD, FP8>), dim3(S, Hkv, B),  \
+                     dim3(PV_WAVES * 64), 0, cur_stream(),                  \
+                     (const short*)q.data_ptr(),                            \
+                     (const void*)k_cache.data_ptr(),                       \
+                     (const void*)v_cache.data_ptr(),                       \
+                     block_table.data_ptr<int>(), ctx_lens.data_ptr<int>(), \
+                     q_lens.data_ptr<int>(), (short*)out.data_ptr(), ws_o,  \
+                     ws_ml, Tq, Hkv, rep_shift, (int)k_cache.size(0),       \
+                     (int)block_table.size(1),                              \
+                     1.0f / sqrtf((float)D) * (float)k_scale,               \
+                     (float)v_scale)
+#define PV_LAUNCH(DD)                                                       \
+  if (fp8) { PV_LAUNCH_T(DD, true); } else { PV_LAUNCH_T(DD, false); }
+  if (D == 64) { PV_LAUNCH(64); } else { PV_LAUNCH(128); }
+#undef PV_LAUNCH
+#undef PV_LAUNCH_T
+  if (S > 1) launch_paged_reduce(ws, out, B, Tq * Hq, D, S);
+  return out;
+}
+
+// q [B,Tq,Hq,D], k/v [B,Tq,Hkv,D]: contiguous or slices of a fused QKV
+// row (contiguous [H,D] tail, 16-byte-aligned batch and token strides).
+static void paged_row_strides4(const at::Tensor& t, const char* name,
+                               long long* bs, long long* ts) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1 && t.stride(2) == t.size(3),
+              name, " must be [B, Tq, H, D] with a contiguous [H, D] tail");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && aligned16(t),
+              name, " rows must be 16-byte aligned");
+  *bs = (long long)t.stride(0);
+  *ts = (long long)t.stride(1);
+}
+
+// The verify step's RoPE + append: row (b, i) at position pos0[b] + i,
+// written for pos0[b] >= 0 and i < q_lens[b] only. Returns rotated q.
+at::Tensor rope_append_paged_multi(at::Tensor q, at::Tensor k, at::Tensor v,
+                                   at::Tensor cosT, at::Tensor sinT,
+                                   at::Tensor pos0, at::Tensor q_lens,
+                                   at::Tensor block_table, at::Tensor k_cache,
+                                   at::Tensor v_cache, double k_scale,
+                                   double v_scale) {
+  long long q_bs, q_ts, k_bs, k_ts, v_bs, v_ts;
+  paged_row_strides4(q, "q", &q_bs, &q_ts);
+  paged_row_strides4(k, "k", &k_bs, &k_ts);
+  paged_row_strides4(v, "v", &v_bs, &v_ts);
+  CHECK_IN(cosT); CHECK_IN(sinT);
+  CHECK_I32(pos0);
+  CHECK_I32(q_lens);
+  CHECK_I32(block_table);
+  int B = (int)q.size(0), Hq = (int)q.size(2), D = (int)q.size(3);
+  int Hkv = (int)k.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "paged_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(q.size(1) >= 1 && q.size(1) <= 65535 && q.size(0) <= 65535,
+              "rope_append_paged_multi: B and Tq must fit a grid dimension");
+  int Tq = (int)q.size(1);
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(1) == Tq &&
+              v.size(1) == Tq && k.size(3) == D && v.size(3) == D &&
+              v.size(2) == Hkv,
+              "q/k/v shapes disagree");
+  const bool fp8 = check_paged_cache(k_cache, v_cache, Hkv, D, k_scale,
+                                     v_scale);
+  TORCH_CHECK(cosT.scalar_type() == at::kFloat &&
+              sinT.scalar_type() == at::kFloat && cosT.dim() == 2 &&
+              cosT.size(1) == D / 2 && sinT.sizes() == cosT.sizes(),
+              "cosT/sinT must be fp32 [T, D/2]");
+  TORCH_CHECK(pos0.dim() == 1 && pos0.size(0) == B && q_lens.dim() == 1 &&
+              q_lens.size(0) == B, "pos0 and q_lens must be [B]");
+  TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == B &&
+              block_table.size(1) >= 1,
+              "block_table must be [B, max_pages]");
+  auto q_rot = at::empty({B, Tq, Hq, D}, q.options());
+  if (B == 0) return q_rot;
+#define RM_LAUNCH(FP8)                                                      \
+  hipLaunchKernelGGL(rope_append_paged_multi_kernel<FP8>, dim3(Tq, B),      \
+                     dim3(256), 0, cur_stream(),                            \
+                     (const short*)q.data_ptr(), (const short*)k.data_ptr(),\
+                     (const short*)v.data_ptr(), q_bs, q_ts, k_bs, k_ts,    \
+                     v_bs, v_ts, cosT.data_ptr<float>(),                    \
+                     sinT.data_ptr<float>(), pos0.data_ptr<int>(),          \
+                     q_lens.data_ptr<int>(), block_table.data_ptr<int>(),   \
+                     k_cache.data_ptr(), v_cache.data_ptr(),                \
+                     (short*)q_rot.data_ptr(), Hq, Hkv, D,                  \
+                     (int)cosT.size(0), (int)k_cache.size(0),               \
+                     (int)block_table.size(1), (float)(1.0 / k_scale),      \
+                     (float)(1.0 / v_scale))
+  if (fp8) { RM_LAUNCH(true); } else { RM_LAUNCH(false); }
+#undef RM_LAUNCH
+  return q_rot;
+}
+
 // ---------------- weight-gradient GEMM ----------------
 
 // [rows, cols] bf16, unit column stride, 16-byte-aligned rows (a column
@@ -1532,6 +1685,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
         py::arg("ctx_lens"), py::arg("q_lens"), py::arg("k_scale") = 1.0,
         py::arg("v_scale") = 1.0);
+  m.def("paged_attn_verify", &paged_attn_verify, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("block_table"),
+        py::arg("ctx_lens"), py::arg("q_lens"), py::arg("num_splits") = 1,
+        py::arg("workspace") = py::none(), py::arg("k_scale") = 1.0,
+        py::arg("v_scale") = 1.0);
+  m.def("rope_append_paged_multi", &rope_append_paged_multi);
+  m.attr("verify_max_rows") = PV_MAX_ROWS;
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("rmsnorm_bwd_two_pass", &rmsnorm_bwd_two_pass);
   m.def("rmsnorm_bwd_res", &rmsnorm_bwd_res, py::arg("dy"), py::arg("x"),

@@ -10,7 +10,7 @@ from __future__ import annotations
 import random
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 import torch
 
@@ -89,9 +89,30 @@ class LLMConfig:
     # device-to-host copy (the tokens) instead of one synchronisation and
     # two scalar writes per slot.
     device_sampling: bool = False
+    # ContinuousBatchingEngine with kv_cache="paged" only, and not together
+    # with device_sampling. num_speculative_tokens = K > 0: a step runs
+    # each greedy request's last token plus up to K draft tokens through the
+    # model at once (PagedDecoder.verify) and keeps the drafts the model
+    # agrees with, so its tokens are those of K = 0 in fewer steps.
+    # (K + 1) * (num_heads // num_kv_heads) must be <= ops.VERIFY_MAX_ROWS.
+    # speculative_proposer(tokens so far, k) returns up to k draft tokens;
+    # None is prompt lookup: what followed the most recent earlier occurrence
+    # of the last n tokens, n from speculative_ngram down to 1. Requests
+    # that sample (temperature > 0, top-k, top-p or a seed) are not
+    # speculated: they take one token per step, drawn exactly as with K = 0.
+    num_speculative_tokens: int = 0
+    speculative_ngram: int = 3
+    speculative_proposer: Optional[Callable[[List[int], int],
+                                            List[int]]] = None
 
     def __post_init__(self):
         _check_sampling(self.top_k, self.top_p)
+        if (int(self.num_speculative_tokens) != self.num_speculative_tokens
+                or self.num_speculative_tokens < 0):
+            raise ValueError("num_speculative_tokens must be an integer "
+                             f">= 0, got {self.num_speculative_tokens!r}")
+        if self.speculative_ngram < 1:
+            raise ValueError("speculative_ngram must be at least 1")
 
 
 def _check_sampling(top_k, top_p):
@@ -163,6 +184,19 @@ def _lora_rank(config: LLMConfig) -> int:
                      f"{config.max_lora_rank!r}")
 
 
+def ngram_propose(tokens: List[int], k: int, ngram: int = 3) -> List[int]:
+    """Prompt-lookup drafts: for n from `ngram` down to 1, find the most
+    recent earlier occurrence of the last n tokens and return the up to k
+    tokens that followed it; [] when no n matches."""
+    L = len(tokens)
+    for n in range(min(ngram, L - 1), 0, -1):
+        tail = tokens[L - n:]
+        for start in range(L - n - 1, -1, -1):
+            if tokens[start:start + n] == tail:
+                return tokens[start + n:start + n + k]
+    return []
+
+
 def _quantized_weights(config: LLMConfig):
     """None for model-dtype weights, else "fp8" or "mxfp4"."""
     if config.weight_dtype not in _WEIGHT_DTYPES:
@@ -185,6 +219,9 @@ class LLMEngine(_Sampling):
         if _lora_rank(config):
             raise ValueError("max_loras needs ContinuousBatchingEngine "
                              "with kv_cache='paged'")
+        if config.num_speculative_tokens:
+            raise ValueError("num_speculative_tokens needs "
+                             "ContinuousBatchingEngine with kv_cache='paged'")
         cfg = CONFIGS[config.model_id]
         self.model_cfg = cfg
         self.device = (
@@ -345,6 +382,17 @@ class ContinuousBatchingEngine(_Sampling):
             if not self._paged:
                 raise ValueError("max_loras needs kv_cache='paged'")
             add_lora_slots(self.model, config.max_loras, self._lora_rank)
+        self._spec = int(config.num_speculative_tokens)
+        if self._spec:
+            if not self._paged:
+                raise ValueError(
+                    "num_speculative_tokens needs kv_cache='paged'")
+            if config.device_sampling:
+                raise ValueError("num_speculative_tokens together with "
+                                 "device_sampling is not built yet")
+            self._propose = config.speculative_proposer or (
+                lambda toks, k: ngram_propose(toks, k,
+                                              config.speculative_ngram))
         if self._paged:
             from ray_amd.llm.paged import PagedDecoder
 
@@ -357,7 +405,8 @@ class ContinuousBatchingEngine(_Sampling):
                                             config.prefill_chunk_tokens),
                                         kv_dtype=kv_dtype,
                                         k_scale=config.kv_k_scale,
-                                        v_scale=config.kv_v_scale)
+                                        v_scale=config.kv_v_scale,
+                                        spec_tokens=self._spec)
             if config.use_hip_graph and self.device.type == "cuda":
                 self.decoder.capture()
         else:
@@ -386,6 +435,9 @@ class ContinuousBatchingEngine(_Sampling):
                       "decode_steps": 0}
         if self._lora_rank:
             self.stats["loras_loaded"] = 0
+        if self._spec:
+            self.stats["spec_draft_tokens"] = 0
+            self.stats["spec_accepted_tokens"] = 0
         self.stats["weight_bytes"] = sum(
             t.numel() * t.element_size()
             for t in (*self.model.parameters(), *self.model.buffers()))
@@ -578,6 +630,11 @@ class ContinuousBatchingEngine(_Sampling):
         if not active:
             out, self._finished = self._finished, []
             return out
+        if self._spec:
+            self._spec_step(active)
+            self.stats["decode_steps"] += 1
+            out, self._finished = self._finished, []
+            return out
         if self.config.device_sampling:
             sampled = self._decode_and_sample(active)
         else:
@@ -601,6 +658,72 @@ class ContinuousBatchingEngine(_Sampling):
         self.stats["decode_steps"] += 1
         out, self._finished = self._finished, []
         return out
+
+    def _draft(self, r: dict) -> List[int]:
+        """Draft tokens for one request this step: none unless it is greedy
+        (argmax of the raw logits), and so few that the step neither emits
+        more than the request's remaining tokens nor writes a row at or
+        past max_T - 1."""
+        if r["temperature"] > 0 or r["filtered"]:
+            return []
+        room = min(self._spec, r["max_new_tokens"] - len(r["out"]) - 1,
+                   self.max_T - 2 - r["pos"])
+        if room <= 0:
+            return []
+        draft = []
+        for t in list(self._propose(r["prompt"] + r["out"], room))[:room]:
+            if not 0 <= int(t) < self.model_cfg.vocab_size:
+                break
+            draft.append(int(t))
+        return draft
+
+    def _spec_step(self, active: List[int]):
+        """One verify step: row 0 of a slot is the request's last token, the
+        rows after it its drafts. A greedy request keeps the drafts that
+        equal the argmax of the row before them and then takes the argmax
+        of the first row that disagrees (of the last row when all agree),
+        which are the tokens single steps would have produced. The others
+        have one row, sampled as in a plain step."""
+        T = self._spec + 1
+        ps = self.decoder.pool.page_size
+        toks = [[0] * T for _ in range(self.B)]
+        ctx = [0] * self.B
+        q_lens = [0] * self.B
+        drafts = {}
+        for s in active:
+            r = self._slots[s]
+            d = drafts[s] = self._draft(r)
+            # every row the step writes lies inside the slot's pages
+            if r["pos"] + len(d) >= ps * len(self.decoder._slot_pages[s]):
+                raise RuntimeError(
+                    f"request {r['id']}: rows up to {r['pos'] + len(d)} "
+                    f"exceed the slot's reserved pages")
+            toks[s][: len(d) + 1] = [r["out"][-1], *d]
+            ctx[s] = r["pos"]
+            q_lens[s] = len(d) + 1
+        logits = self.decoder.verify(
+            torch.tensor(toks, device=self.device),
+            torch.tensor(ctx, dtype=torch.int32, device=self.device),
+            torch.tensor(q_lens, dtype=torch.int32, device=self.device))
+        top = logits.argmax(-1).tolist()  # [B][T], the step's one read
+        for s in active:
+            r = self._slots[s]
+            d = drafts[s]
+            if r["temperature"] > 0 or r["filtered"]:
+                new = [self._sample_request(logits[s, 0], r)]
+            else:
+                n = 0
+                while n < len(d) and d[n] == top[s][n]:
+                    n += 1
+                new = d[:n] + [top[s][n]]
+                self.stats["spec_draft_tokens"] += len(d)
+                self.stats["spec_accepted_tokens"] += n
+            r["out"].extend(new)
+            r["pos"] += len(new)
+            self.decoder.set_slot_len(s, r["pos"])
+            if (len(r["out"]) >= r["max_new_tokens"]
+                    or r["pos"] >= self.max_T - 1):
+                self._retire(s)
 
     def _decode_and_sample(self, active: List[int]) -> List[int]:
         """device_sampling: one decode step and one ops.sample call for the

@@ -238,9 +238,19 @@ class PagedDecoder:
                  prefix_caching: bool = False,
                  prefill_chunk: Optional[int] = None,
                  kv_dtype: Optional[torch.dtype] = None,
-                 k_scale: float = 1.0, v_scale: float = 1.0):
+                 k_scale: float = 1.0, v_scale: float = 1.0,
+                 spec_tokens: int = 0):
         if prefill_chunk is not None and prefill_chunk < 1:
             raise ValueError("prefill_chunk must be at least 1")
+        if spec_tokens < 0:
+            raise ValueError("spec_tokens must be >= 0")
+        rep = model.cfg.num_heads // model.cfg.num_kv_heads
+        if spec_tokens and (spec_tokens + 1) * rep > ops.VERIFY_MAX_ROWS:
+            raise ValueError(
+                f"spec_tokens={spec_tokens} needs (spec_tokens + 1) * "
+                f"(num_heads // num_kv_heads) <= {ops.VERIFY_MAX_ROWS}; this "
+                f"model's ratio is {rep}")
+        self.spec_tokens = spec_tokens
         self.prefix_caching = prefix_caching
         self.prefill_chunk = prefill_chunk
         self.prefix_hit_tokens = 0        # prompt tokens served from pages
@@ -283,6 +293,25 @@ class PagedDecoder:
                 dtype=torch.float32, device=device)
         self.out_logits = None
         self.graph = None
+        if spec_tokens:
+            # the verify step's static state: K+1 rows per slot
+            T = spec_tokens + 1
+            self.in_toks = torch.zeros(batch_size, T, dtype=torch.long,
+                                       device=device)
+            self.ctx = torch.zeros(batch_size, dtype=torch.int32,
+                                   device=device)
+            self.q_lens = torch.zeros(batch_size, dtype=torch.int32,
+                                      device=device)
+            # each slot's adapter, once per row of the slot
+            self.row_lora = torch.full((batch_size * T,), -1,
+                                       dtype=torch.int32, device=device)
+            self.verify_workspace = None
+            if device.type == "cuda" and self.num_splits > 1:
+                self.verify_workspace = torch.empty(
+                    batch_size * T * cfg.num_heads * self.num_splits
+                    * (hd + 2), dtype=torch.float32, device=device)
+            self.verify_logits = None
+            self.verify_graph = None
 
     # ---- slot bookkeeping -------------------------------------------
 
@@ -310,6 +339,9 @@ class PagedDecoder:
         if self._slot_lora[slot] != lora_slot:
             self._slot_lora[slot] = lora_slot
             self.slot_lora[slot] = lora_slot
+            if self.spec_tokens:
+                T = self.spec_tokens + 1
+                self.row_lora[slot * T:(slot + 1) * T] = lora_slot
 
     def _row_lora(self, slot: int, T: int):
         """state.idx of a prefill of T rows of `slot`: None for the base."""
@@ -543,6 +575,18 @@ class PagedDecoder:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out_logits = self._step()
+        if self.spec_tokens:
+            # the verify step as a second graph, recorded the same way;
+            # q_lens is all zero here, so the warm-up writes no K/V
+            self.q_lens.zero_()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self.verify_logits = self._verify_step()
+            torch.cuda.current_stream().wait_stream(s)
+            self.verify_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.verify_graph):
+                self.verify_logits = self._verify_step()
 
     @torch.no_grad()
     def decode(self, toks: torch.Tensor, pos: torch.Tensor):
@@ -557,3 +601,66 @@ class PagedDecoder:
             self.graph.replay()
             return self.out_logits
         return self._step()
+
+    # ---- speculative verify -----------------------------------------
+
+    def _verify_step(self):
+        if self.lora_state is None:
+            return self._verify_rows()
+        self.lora_state.idx = self.row_lora
+        try:
+            return self._verify_rows()
+        finally:
+            self.lora_state.idx = None
+
+    def _verify_rows(self):
+        """_step_rows with K+1 rows per slot: row i of slot b is the token
+        at position ctx[b] + i. Append-then-attend, so a row sees the rows
+        before it of the same call."""
+        m = self.m
+        B, T = self.in_toks.shape
+        pool = self.pool
+        x = m.embed(self.in_toks)  # [B,T,H]
+        lin = ops.linear_sb
+        for li, layer in enumerate(m.layers):
+            h = layer.attn_norm(x)
+            at = layer.attn
+            q, k, v = at.qkv(h, lin=lin)  # strided views of the fused rows
+            kp, vp = pool.k[li], pool.v[li]
+            q = ops.rope_append_paged_multi(
+                q, k, v, m.cosT, m.sinT, self.ctx, self.q_lens,
+                self.block_table, kp, vp, pool.k_scale, pool.v_scale)
+            attn = ops.paged_attention_verify(
+                q, kp, vp, self.block_table, self.ctx, self.q_lens,
+                num_splits=self.num_splits, workspace=self.verify_workspace,
+                k_scale=pool.k_scale, v_scale=pool.v_scale)
+            x = x + proj(at.o_proj, attn.reshape(B, T, -1), lin)
+            hm = layer.mlp_norm(x)
+            mp = layer.mlp
+            x = x + proj(mp.down_proj,
+                         ops.swiglu(proj(mp.gate_proj, hm, lin),
+                                    proj(mp.up_proj, hm, lin)), lin)
+        x = m.final_norm(x)
+        return proj(m.lm_head, x, lin)
+
+    @torch.no_grad()
+    def verify(self, toks: torch.Tensor, ctx: torch.Tensor,
+               q_lens: torch.Tensor):
+        """toks [B, K+1]: each slot's last token followed by its drafts;
+        ctx [B]: the position of row 0, which is the rows the slot already
+        holds; q_lens [B]: valid rows per slot (0: the slot sits out).
+        Returns logits [B, K+1, V]: row i predicts position ctx + i + 1.
+        Rows i < q_lens[b] write their K/V at ctx[b] + i; the other rows
+        write nothing and their logits are meaningless. seq_lens is not
+        touched: the caller sets each slot's length once it knows how many
+        rows it accepts. Rejected rows stay in the pages past that length,
+        are never read and are overwritten by the next step."""
+        if not self.spec_tokens:
+            raise ValueError("verify needs PagedDecoder(spec_tokens > 0)")
+        self.in_toks.copy_(toks.view(self.B, self.spec_tokens + 1))
+        self.ctx.copy_(ctx.to(device=self.device, dtype=torch.int32))
+        self.q_lens.copy_(q_lens.to(device=self.device, dtype=torch.int32))
+        if self.verify_graph is not None:
+            self.verify_graph.replay()
+            return self.verify_logits
+        return self._verify_step()

@@ -1452,6 +1452,76 @@ def paged_attention_prefill(q, k_cache, v_cache, block_table, ctx_lens,
 
 
 # --------------------------------------------------------------------------
+# Paged-KV verify attention for speculative decoding
+# (csrc/hip/paged_attn_verify.hip)
+# --------------------------------------------------------------------------
+
+# Tq * (Hq // Hkv) of one verify call: the query columns of one MFMA tile
+VERIFY_MAX_ROWS = 32
+
+
+def paged_attention_verify(q, k_cache, v_cache, block_table, ctx_lens,
+                           q_lens, num_splits=None, workspace=None,
+                           k_scale=1.0, v_scale=1.0):
+    """Causal attention from a few query tokens per sequence (a verify
+    step's last token and drafts) to a paged KV cache, split over KV like
+    paged_attention_decode. Semantics, shapes and reference are those of
+    paged_attention_prefill (the CPU path is paged_attention_prefill_ref);
+    Tq * (Hq // Hkv) <= VERIFY_MAX_ROWS. num_splits=None picks a value from
+    the block table's capacity; graph-capturing callers pass a fixed value
+    and, for num_splits > 1, a static fp32 `workspace` of
+    B*Tq*Hq*num_splits*(D+2) elements."""
+    if not q.is_cuda:
+        return paged_attention_prefill_ref(q, k_cache, v_cache, block_table,
+                                           ctx_lens, q_lens, k_scale, v_scale)
+    _require_ext("paged_attention_verify")
+    if num_splits is None:
+        num_splits = default_num_splits(
+            q.shape[0], k_cache.shape[1],
+            block_table.shape[1] * k_cache.shape[2], q.device)
+    return _K.paged_attn_verify(q, k_cache, v_cache, block_table, ctx_lens,
+                                q_lens, int(num_splits), workspace,
+                                float(k_scale), float(v_scale))
+
+
+def rope_append_paged_multi_ref(q, k, v, cosT, sinT, pos0, q_lens,
+                                block_table, k_cache, v_cache, k_scale=1.0,
+                                v_scale=1.0):
+    """Reference for rope_append_paged_multi: rope_append_paged_ref row by
+    row, token i of sequence b at position pos0[b] + i, skipped (zero
+    q_rot, no write) where pos0[b] < 0 or i >= q_lens[b]."""
+    B, Tq = q.shape[:2]
+    q_rot = torch.zeros(q.shape, dtype=q.dtype, device=q.device)
+    live = pos0 >= 0
+    for i in range(Tq):
+        pos = torch.where(live & (q_lens > i), pos0 + i,
+                          torch.full_like(pos0, -1))
+        q_rot[:, i] = rope_append_paged_ref(
+            q[:, i], k[:, i], v[:, i], cosT, sinT, pos, block_table, k_cache,
+            v_cache, k_scale, v_scale)
+    return q_rot
+
+
+def rope_append_paged_multi(q, k, v, cosT, sinT, pos0, q_lens, block_table,
+                            k_cache, v_cache, k_scale=1.0, v_scale=1.0):
+    """Fused verify-step RoPE + paged KV append (one launch). q
+    [B,Tq,Hq,D], k/v [B,Tq,Hkv,D] (fused-QKV slices accepted as they
+    are), pos0 [B] int32 position of each sequence's row 0 (-1: inactive),
+    q_lens [B] int32 rows to write. Row (b, i) is rotated at pos0[b] + i;
+    rotated k and raw v go to the pages for i < q_lens[b]. Updates the
+    caches in place, returns rotated q [B,Tq,Hq,D] (zeros for rows that are
+    not written)."""
+    if not q.is_cuda:
+        return rope_append_paged_multi_ref(q, k, v, cosT, sinT, pos0, q_lens,
+                                           block_table, k_cache, v_cache,
+                                           k_scale, v_scale)
+    _require_ext("rope_append_paged_multi")
+    return _K.rope_append_paged_multi(q, k, v, cosT, sinT, pos0, q_lens,
+                                      block_table, k_cache, v_cache,
+                                      float(k_scale), float(v_scale))
+
+
+# --------------------------------------------------------------------------
 # Token sampling: temperature, top-k, top-p, inverse-CDF draw
 # --------------------------------------------------------------------------
 
