@@ -26,6 +26,7 @@
 #include "hip/linear_w4.hip"
 #include "hip/linear_w4_gemm.hip"
 #include "hip/lora.hip"
+#include "hip/moe.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/paged_attn_verify.hip"
@@ -736,6 +737,141 @@ at::Tensor lora_add(at::Tensor y, at::Tensor x, at::Tensor A, at::Tensor B,
   else if (R == 32) { LORA_LAUNCH(32); }
   else { LORA_LAUNCH(64); }
 #undef LORA_LAUNCH
+  HIP_CHECK_KERNEL();
+  return y;
+}
+
+// ---------------- mixture-of-experts FFN ----------------
+
+// Words of the pair lists of csrc/hip/moe.hip for P = M*k pairs and E
+// experts: 3 words a group, G = ceil(P/64) + E groups, then the P pairs.
+static inline long long moe_groups(long long P, long long E) {
+  return (P + 63) / 64 + E;
+}
+
+static void moe_check_idx(const at::Tensor& idx, long long E, const char* who) {
+  CHECK_IN(idx);
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.dim() == 2, who,
+              ": idx must be int32 [M, k]");
+  const long long M = idx.size(0), k = idx.size(1);
+  TORCH_CHECK(M >= 1 && M <= 65536, who, ": 1 to 65536 rows");
+  TORCH_CHECK(E >= 2 && E <= MOE_MAX_E, who, ": 2 to 64 experts");
+  TORCH_CHECK(k >= 1 && k <= MOE_MAX_K && k <= E, who,
+              ": top_k must be 1..8 and at most the number of experts");
+}
+
+// idx [M, k] int32 -> the per-expert pair lists, built on the device by one
+// block in a fixed order. Entries outside 0..E-1 are in no list.
+at::Tensor moe_align(at::Tensor idx, int64_t E) {
+  moe_check_idx(idx, E, "moe_align");
+  const long long P = idx.numel(), G = moe_groups(P, E);
+  auto lists = at::empty({3 * G + P}, idx.options());
+  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_ALIGN_THREADS), 0,
+                     cur_stream(), idx.data_ptr<int>(), lists.data_ptr<int>(),
+                     (int)P, (int)E, (int)G);
+  HIP_CHECK_KERNEL();
+  return lists;
+}
+
+// x [M, H], router_w [E, H] bf16 -> idx [M, k] int32, w [M, k] fp32 and the
+// pair lists of idx.
+std::vector<at::Tensor> moe_route(at::Tensor x, at::Tensor router_w,
+                                  int64_t top_k) {
+  CHECK_IN(x); CHECK_IN(router_w);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+                  router_w.scalar_type() == at::kBFloat16,
+              "moe_route: x and router_w must be bf16");
+  TORCH_CHECK(x.dim() == 2 && router_w.dim() == 2 &&
+                  router_w.size(1) == x.size(1),
+              "moe_route: x [M, H], router_w [E, H]");
+  const long long M = x.size(0), H = x.size(1), E = router_w.size(0);
+  TORCH_CHECK(H > 0 && H % 128 == 0, "moe_route: H must be a multiple of 128");
+  TORCH_CHECK(aligned16(x) && aligned16(router_w),
+              "moe_route: x and router_w must be 16-byte aligned");
+  TORCH_CHECK(top_k >= 1 && top_k <= MOE_MAX_K, "moe_route: top_k must be 1..8");
+  auto idx = at::empty({M, top_k}, x.options().dtype(at::kInt));
+  moe_check_idx(idx, E, "moe_route");
+  auto w = at::empty({M, top_k}, x.options().dtype(at::kFloat));
+  hipLaunchKernelGGL(moe_route_kernel, dim3((unsigned)((M + 3) / 4)),
+                     dim3(256), 0, cur_stream(), (const short*)x.data_ptr(),
+                     (const short*)router_w.data_ptr(), idx.data_ptr<int>(),
+                     w.data_ptr<float>(), (int)M, (int)H, (int)E, (int)top_k);
+  HIP_CHECK_KERNEL();
+  return {idx, w, moe_align(idx, E)};
+}
+
+// y[m] = bf16(sum_j w[m, j] * ffn_{idx[m, j]}(x[m]) (+ residual[m])), the
+// expert FFNs of csrc/hip/moe.hip over the lists of moe_align(idx, E). The
+// workspaces (h [M*k, I] bf16, ws [M*k, H] fp32) come from the caching
+// allocator with sizes that depend on the shapes only: safe under capture.
+at::Tensor moe_experts(at::Tensor x, at::Tensor idx, at::Tensor w,
+                       at::Tensor lists, at::Tensor w_gate, at::Tensor w_up,
+                       at::Tensor w_down, c10::optional<at::Tensor> residual) {
+  CHECK_IN(x); CHECK_IN(w); CHECK_IN(lists); CHECK_IN(w_gate); CHECK_IN(w_up);
+  CHECK_IN(w_down);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+                  w_gate.scalar_type() == at::kBFloat16 &&
+                  w_up.scalar_type() == at::kBFloat16 &&
+                  w_down.scalar_type() == at::kBFloat16,
+              "moe_experts: x and the expert weights must be bf16");
+  TORCH_CHECK(x.dim() == 2 && w_gate.dim() == 3 && w_up.dim() == 3 &&
+                  w_down.dim() == 3,
+              "moe_experts: x [M, H], w_gate, w_up [E, I, H], w_down "
+              "[E, H, I]");
+  const long long M = x.size(0), H = x.size(1);
+  const long long E = w_gate.size(0), I = w_gate.size(1);
+  moe_check_idx(idx, E, "moe_experts");
+  const long long k = idx.size(1), P = M * k, G = moe_groups(P, E);
+  TORCH_CHECK(H > 0 && H % 128 == 0 && I > 0 && I % 128 == 0,
+              "moe_experts: H and I must be multiples of 128");
+  TORCH_CHECK(idx.size(0) == M && w.scalar_type() == at::kFloat &&
+                  w.dim() == 2 && w.size(0) == M && w.size(1) == k &&
+                  w_gate.size(2) == H && w_up.size(0) == E &&
+                  w_up.size(1) == I && w_up.size(2) == H &&
+                  w_down.size(0) == E && w_down.size(1) == H &&
+                  w_down.size(2) == I,
+              "moe_experts: shapes do not match");
+  TORCH_CHECK(lists.scalar_type() == at::kInt && lists.dim() == 1 &&
+                  lists.size(0) == 3 * G + P,
+              "moe_experts: lists must come from moe_align for this idx");
+  TORCH_CHECK(aligned16(x) && aligned16(w_gate) && aligned16(w_up) &&
+                  aligned16(w_down),
+              "moe_experts: x and the expert weights must be 16-byte aligned");
+  const short* res = nullptr;
+  if (residual.has_value()) {
+    const at::Tensor& r = *residual;
+    CHECK_IN(r);
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 &&
+                    r.size(0) == M && r.size(1) == H && aligned16(r),
+                "moe_experts: residual must be bf16 [M, H], 16-byte aligned");
+    res = (const short*)r.data_ptr();
+  }
+  auto h = at::empty({P, I}, x.options());
+  auto ws = at::empty({P, H}, x.options().dtype(at::kFloat));
+  auto y = at::empty({M, H}, x.options());
+  // 32 channels a block once the gathered rows outweigh the weights (the
+  // rows are read once per channel slice); the result does not depend on it
+#define MOE_LAUNCH(NTI)                                                      \
+  hipLaunchKernelGGL((moe_gate_up_kernel<NTI>),                              \
+                     dim3((unsigned)(I / (16 * NTI)), (unsigned)G),          \
+                     dim3(512), 0, cur_stream(), (const short*)x.data_ptr(), \
+                     (const short*)w_gate.data_ptr(),                        \
+                     (const short*)w_up.data_ptr(), lists.data_ptr<int>(),   \
+                     (short*)h.data_ptr(), (int)k, (int)H, (int)I, (int)G);  \
+  hipLaunchKernelGGL((moe_down_kernel<NTI>),                                 \
+                     dim3((unsigned)(H / (16 * NTI)), (unsigned)G),          \
+                     dim3(512), 0, cur_stream(), (const short*)h.data_ptr(), \
+                     (const short*)w_down.data_ptr(), w.data_ptr<float>(),   \
+                     lists.data_ptr<int>(), ws.data_ptr<float>(), (int)H,    \
+                     (int)I, (int)G)
+  if (P >= 256) { MOE_LAUNCH(2); }
+  else { MOE_LAUNCH(1); }
+#undef MOE_LAUNCH
+  const long long total = M * (H / 4);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((total + 255) / 256)),
+                     dim3(256), 0, cur_stream(), ws.data_ptr<float>(),
+                     idx.data_ptr<int>(), res, (short*)y.data_ptr(), total,
+                     (int)k, (int)H, (int)E);
   HIP_CHECK_KERNEL();
   return y;
 }
@@ -1663,6 +1799,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scales"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("lora_add", &lora_add, py::arg("y"), py::arg("x"), py::arg("A"),
         py::arg("B"), py::arg("scale"), py::arg("idx"), py::arg("split") = 0);
+  m.def("moe_align", &moe_align, py::arg("idx"), py::arg("num_experts"));
+  m.def("moe_route", &moe_route, py::arg("x"), py::arg("router_w"),
+        py::arg("top_k"));
+  m.def("moe_experts", &moe_experts, py::arg("x"), py::arg("idx"),
+        py::arg("w"), py::arg("lists"), py::arg("w_gate"), py::arg("w_up"),
+        py::arg("w_down"), py::arg("residual") = py::none());
   m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),

@@ -29,6 +29,9 @@ from ray_amd.models.llama import (
 
 @dataclass
 class LLMConfig:
+    # A key of models.llama.CONFIGS. "mixtral-8x7b" and "moe-tiny" are
+    # mixture-of-experts models: ContinuousBatchingEngine with
+    # kv_cache="paged" only, expert weights in bf16 (ops.moe_ffn).
     model_id: str = "llama-tiny"
     max_seq_len: int = 512
     max_batch_size: int = 1
@@ -223,6 +226,9 @@ class LLMEngine(_Sampling):
             raise ValueError("num_speculative_tokens needs "
                              "ContinuousBatchingEngine with kv_cache='paged'")
         cfg = CONFIGS[config.model_id]
+        if cfg.num_experts:
+            raise ValueError("a model with experts needs "
+                             "ContinuousBatchingEngine with kv_cache='paged'")
         self.model_cfg = cfg
         self.device = (
             torch.device("cuda", 0)
@@ -367,9 +373,14 @@ class ContinuousBatchingEngine(_Sampling):
         if kv_dtype == torch.float8_e4m3fn and not self._paged:
             raise ValueError("kv_cache_dtype='fp8' needs kv_cache='paged'")
         wq = _quantized_weights(config)
+        if cfg.num_experts and not self._paged:
+            raise ValueError("a model with experts needs kv_cache='paged'")
         if wq:
             if not self._paged:
                 raise ValueError(f"weight_dtype='{wq}' needs kv_cache='paged'")
+            if cfg.num_experts:
+                raise ValueError(f"weight_dtype='{wq}' together with a model "
+                                 "with experts is not built yet")
             if wq == "fp8":
                 quantize_linears_fp8(self.model)
             else:

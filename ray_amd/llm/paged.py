@@ -15,7 +15,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ray_amd import ops
-from ray_amd.models.llama import proj
+from ray_amd.models.llama import MoEMLP, proj
 
 PAGE_SIZE = ops.PAGE_SIZE
 
@@ -516,6 +516,9 @@ class PagedDecoder:
                                                ctx_lens, q_lens,
                                                pool.k_scale, pool.v_scale)
             x = x + at.o_proj(attn.reshape(1, T, -1))
+            if isinstance(layer.mlp, MoEMLP):
+                x = layer.mlp(layer.mlp_norm(x), residual=x)
+                continue
             x = x + layer.mlp(layer.mlp_norm(x))
         if not last:
             return None
@@ -554,6 +557,9 @@ class PagedDecoder:
             x = x + proj(at.o_proj, attn.reshape(B, 1, -1), lin)
             hm = layer.mlp_norm(x)
             mp = layer.mlp
+            if isinstance(mp, MoEMLP):
+                x = mp(hm, residual=x)
+                continue
             x = x + proj(mp.down_proj,
                          ops.swiglu(proj(mp.gate_proj, hm, lin),
                                     proj(mp.up_proj, hm, lin)), lin)
@@ -637,6 +643,9 @@ class PagedDecoder:
             x = x + proj(at.o_proj, attn.reshape(B, T, -1), lin)
             hm = layer.mlp_norm(x)
             mp = layer.mlp
+            if isinstance(mp, MoEMLP):
+                x = mp(hm, residual=x)
+                continue
             x = x + proj(mp.down_proj,
                          ops.swiglu(proj(mp.gate_proj, hm, lin),
                                     proj(mp.up_proj, hm, lin)), lin)

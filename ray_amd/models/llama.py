@@ -34,6 +34,10 @@ class LlamaConfig:
     rope_base: float = 500000.0
     rms_eps: float = 1e-5
     tie_embeddings: bool = False
+    # num_experts > 0: every block's FFN is a MoEMLP of that many experts,
+    # num_experts_per_tok of them per token; 0: the dense MLP
+    num_experts: int = 0
+    num_experts_per_tok: int = 2
 
 
 CONFIGS = {
@@ -46,6 +50,18 @@ CONFIGS = {
     "llama-tiny": LlamaConfig(
         vocab_size=512, hidden_size=256, intermediate_size=512,
         num_layers=2, num_heads=4, num_kv_heads=2, max_seq_len=512,
+    ),
+    # Mixtral-8x7B: 8 SwiGLU experts a layer, 2 per token
+    "mixtral-8x7b": LlamaConfig(
+        vocab_size=32000, hidden_size=4096, intermediate_size=14336,
+        num_layers=32, num_heads=32, num_kv_heads=8, max_seq_len=8192,
+        rope_base=1e6, num_experts=8, num_experts_per_tok=2,
+    ),
+    # llama-tiny with 8 experts, 2 per token
+    "moe-tiny": LlamaConfig(
+        vocab_size=512, hidden_size=256, intermediate_size=512,
+        num_layers=2, num_heads=4, num_kv_heads=2, max_seq_len=512,
+        num_experts=8, num_experts_per_tok=2,
     ),
 }
 
@@ -77,7 +93,8 @@ def quantize_linears_fp8(model: "LlamaModel") -> "LlamaModel":
     The embedding and the norms keep the model dtype; a tied lm_head is
     quantised from the embedding's values and no longer shares them. The
     model then serves inference only, through PagedDecoder or its own
-    forward."""
+    forward. A MoEMLP has none of the dense projections: its expert weights
+    and router stay in the model dtype."""
     return _quantize_linears(model, ops.LinearW8)
 
 
@@ -114,7 +131,9 @@ def add_lora_slots(model: "LlamaModel", max_loras: int,
     (16, 32 or 64). Returns the state the wrappers share, also kept as
     model.lora_state: set its `idx` to the int32 row -> slot tensor of a
     call (-1: no adapter) to apply the adapters, None to run the base alone. The model then serves inference
-    only. Quantise first (quantize_linears_*), then add the slots."""
+    only. Quantise first (quantize_linears_*), then add the slots. On a model
+    with experts (MoEMLP) the adapters apply to the attention projections
+    only."""
     state = ops.LoraState()
     for layer in model.layers:
         for part, names in _LORA_TARGETS.items():
@@ -243,13 +262,42 @@ class MLP(nn.Module):
         return self.down_proj(ops.swiglu(gate, up))
 
 
+class MoEMLP(nn.Module):
+    """Mixtral's sparse FFN: a router picks num_experts_per_tok of
+    num_experts SwiGLU experts per token and mixes them by the softmax over
+    the chosen logits (ops.moe_route_ref / ops.moe_experts_ref). Inference
+    on the GPU runs the routed HIP kernels (ops.moe_ffn); with grad enabled,
+    or off the GPU, the torch composition runs, so training works through
+    autograd."""
+
+    def __init__(self, cfg: LlamaConfig, dtype=torch.bfloat16):
+        super().__init__()
+        E, H, I = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
+        self.top_k = cfg.num_experts_per_tok
+        self.router = nn.Linear(H, E, bias=False, dtype=dtype)
+        self.w_gate = nn.Parameter(torch.empty(E, I, H, dtype=dtype))
+        self.w_up = nn.Parameter(torch.empty(E, I, H, dtype=dtype))
+        self.w_down = nn.Parameter(torch.empty(E, H, I, dtype=dtype))
+        for p in (self.w_gate, self.w_up, self.w_down):
+            nn.init.normal_(p, std=0.02)
+
+    def forward(self, x, residual=None):
+        """The FFN of x [..., H]; `residual` (x's shape) is added before the
+        one rounding to x's dtype."""
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1])
+        r2 = None if residual is None else residual.reshape(-1, shape[-1])
+        return ops.moe_ffn(x2, self.router.weight, self.w_gate, self.w_up,
+                           self.w_down, self.top_k, r2).view(shape)
+
+
 class Block(nn.Module):
     def __init__(self, cfg: LlamaConfig, dtype=torch.bfloat16):
         super().__init__()
         self.attn_norm = ops.RMSNorm(cfg.hidden_size, cfg.rms_eps, dtype)
         self.attn = Attention(cfg, dtype)
         self.mlp_norm = ops.RMSNorm(cfg.hidden_size, cfg.rms_eps, dtype)
-        self.mlp = MLP(cfg, dtype)
+        self.mlp = (MoEMLP if cfg.num_experts > 0 else MLP)(cfg, dtype)
 
     def forward(self, x, cosT, sinT, kv_cache=None, pos0=0):
         x = x + self.attn(self.attn_norm(x), cosT, sinT, kv_cache, pos0)

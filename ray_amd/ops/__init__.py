@@ -712,6 +712,188 @@ class LoraLinear(torch.nn.Module):
         return self.add(self.base(x), x)
 
 
+# --------------------------------------------------------------------------
+# Mixture-of-experts FFN (csrc/hip/moe.hip)
+# --------------------------------------------------------------------------
+
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+MOE_MAX_ROWS = 65536
+# Rows from which moe_ffn, outside graph capture, runs the per-expert
+# hipBLASLt composition instead of the routed kernels (measured in
+# tools/moe_bench.py, PERFORMANCE.md "Mixture of experts"). A captured step
+# has at most 64 * (K + 1) rows and always runs the kernels.
+MOE_COMPOSE_MIN_ROWS = 512
+
+
+def moe_route_ref(x, router_w, top_k: int, dtype=torch.float64):
+    """The routing rule: logits x @ router_w.T in `dtype`, the top_k largest
+    of a row (ties to the lower expert index, slot 0 the largest) and the
+    softmax over those top_k logits. Returns idx [M, k] int32 and w [M, k]
+    in `dtype` (fp32 when `dtype` is narrower)."""
+    wide = dtype if dtype in (torch.float32, torch.float64) else torch.float32
+    logits = x.to(wide) @ router_w.to(wide).t()
+    # a stable descending sort keeps the lower index first among equals
+    order = torch.sort(logits, dim=-1, descending=True, stable=True).indices
+    idx = order[:, :top_k]
+    w = torch.softmax(logits.gather(1, idx), dim=-1)
+    return idx.int(), w
+
+
+def moe_experts_ref(x, idx, w, w_gate, w_up, w_down, dtype=torch.float64):
+    """y[m] = sum_j w[m, j] * (h_j @ w_down[e].T), h_j = silu(x[m] @
+    w_gate[e].T) * (x[m] @ w_up[e].T), e = idx[m, j], one index_select ->
+    matmul -> index_add_ per expert, in `dtype`. In float64 h is kept exact;
+    otherwise h is rounded to bf16 once, like the kernels, and the result is
+    returned unrounded in `dtype`. Entries of idx outside 0..E-1 add nothing."""
+    M, k = idx.shape
+    E = w_gate.shape[0]
+    xw = x.to(dtype)
+    flat = idx.reshape(-1).long()
+    out = torch.zeros(M, k, x.shape[1], dtype=dtype, device=x.device)
+    pairs = out.view(M * k, -1)
+    for e in range(E):
+        p = (flat == e).nonzero().flatten()
+        if p.numel() == 0:
+            continue
+        xe = xw.index_select(0, p // k)
+        h = (torch.nn.functional.silu(xe @ w_gate[e].to(dtype).t())
+             * (xe @ w_up[e].to(dtype).t()))
+        if dtype != torch.float64:
+            h = h.bfloat16().to(dtype)
+        pairs.index_add_(0, p, (h @ w_down[e].to(dtype).t())
+                         * w.reshape(-1)[p].to(dtype).unsqueeze(1))
+    y = out[:, 0].clone()
+    for j in range(1, k):  # slot order, as the combine kernel
+        y += out[:, j]
+    return y
+
+
+def _moe_check(x, E, H, top_k, w_gate=None, w_up=None, w_down=None):
+    if x.dim() != 2 or x.shape[1] != H:
+        raise ValueError(f"moe: x must be [M, {H}], got {tuple(x.shape)}")
+    if not 1 <= x.shape[0] <= MOE_MAX_ROWS:
+        raise ValueError(f"moe: 1 to {MOE_MAX_ROWS} rows, got {x.shape[0]}")
+    if not 2 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError(f"moe: 2 to {MOE_MAX_EXPERTS} experts, got {E}")
+    if not (1 <= top_k <= MOE_MAX_TOP_K and top_k <= E):
+        raise ValueError(f"moe: top_k must be 1..{MOE_MAX_TOP_K} and at most "
+                         f"the {E} experts, got {top_k}")
+    if H % 128:
+        raise ValueError(f"moe: hidden size {H} is not a multiple of 128")
+    if w_gate is None:
+        return
+    I = w_gate.shape[1]
+    if I % 128:
+        raise ValueError(f"moe: expert width {I} is not a multiple of 128")
+    if (tuple(w_gate.shape) != (E, I, H) or tuple(w_up.shape) != (E, I, H)
+            or tuple(w_down.shape) != (E, H, I)):
+        raise ValueError("moe: w_gate and w_up must be [E, I, H] and w_down "
+                         "[E, H, I]")
+    if not (x.dtype == w_gate.dtype == w_up.dtype == w_down.dtype):
+        raise ValueError("moe: x and the expert weights must share a dtype")
+
+
+def _moe_on_device(x) -> bool:
+    return (x.is_cuda and x.dtype == torch.bfloat16
+            and not torch.is_grad_enabled())
+
+
+def moe_route(x, router_w, top_k: int, with_lists: bool = False):
+    """idx [M, k] int32 and w [M, k] fp32 of moe_route_ref for x [M, H] and
+    router_w [E, H]. bf16 GPU operands with grad off run moe_route_kernel;
+    `with_lists` then also returns the per-expert pair lists the expert
+    kernels read (None on the torch path). Everything else computes
+    moe_route_ref in fp32 (fp64 for fp64 operands)."""
+    if router_w.dim() != 2:
+        raise ValueError("moe_route: router_w must be [E, H]")
+    E, H = router_w.shape
+    _moe_check(x, E, H, top_k)
+    if x.dtype != router_w.dtype:
+        raise ValueError("moe_route: x and router_w must share a dtype")
+    if _moe_on_device(x):
+        _require_ext("moe_route")
+        idx, w, lists = _K.moe_route(x.contiguous(), router_w.contiguous(),
+                                     top_k)
+    else:
+        wide = torch.float64 if x.dtype == torch.float64 else torch.float32
+        idx, w = moe_route_ref(x, router_w, top_k, wide)
+        lists = None
+    return (idx, w, lists) if with_lists else (idx, w)
+
+
+def _moe_compose(x, idx, w, w_gate, w_up, w_down, residual):
+    """The torch composition. Off the GPU: moe_experts_ref in fp32 (fp64 for
+    fp64 operands), the kernels' rounding points. bf16 on the GPU with grad
+    off (the large-M dispatch of moe_ffn): three bf16 hipBLASLt GEMMs per
+    expert, which also round gate, up and the down product to bf16."""
+    if _moe_on_device(x):
+        M, k = idx.shape
+        flat = idx.reshape(-1).long()
+        pairs = torch.zeros(M * k, x.shape[1], dtype=torch.float32,
+                            device=x.device)
+        for e in range(w_gate.shape[0]):
+            p = (flat == e).nonzero().flatten()
+            if p.numel() == 0:
+                continue
+            xe = x.index_select(0, p // k)
+            h = swiglu(xe @ w_gate[e].t(), xe @ w_up[e].t())
+            pairs.index_add_(0, p, (h @ w_down[e].t()).float()
+                             * w.reshape(-1)[p].unsqueeze(1))
+        y = pairs.view(M, k, -1).sum(dim=1)
+    else:
+        wide = torch.float64 if x.dtype == torch.float64 else torch.float32
+        y = moe_experts_ref(x, idx, w, w_gate, w_up, w_down, wide)
+    if residual is not None:
+        y = y + residual.to(y.dtype)
+    return y.to(x.dtype)
+
+
+def moe_experts(x, idx, w, w_gate, w_up, w_down, residual=None, lists=None):
+    """The routed expert FFNs: moe_experts_ref for given idx [M, k] and
+    w [M, k], plus `residual` [M, H], rounded once to x's dtype. bf16 GPU
+    operands with grad off run the HIP kernels over `lists` (moe_route's;
+    built from idx on the device when None). Everything else runs the torch
+    composition with the same rounding points."""
+    if w_gate.dim() != 3:
+        raise ValueError("moe_experts: w_gate must be [E, I, H]")
+    E, _, H = w_gate.shape
+    if idx.dim() != 2 or tuple(w.shape) != tuple(idx.shape) \
+            or idx.shape[0] != x.shape[0]:
+        raise ValueError("moe_experts: idx and w must be [M, k]")
+    _moe_check(x, E, H, idx.shape[1], w_gate, w_up, w_down)
+    if residual is not None and (residual.shape != x.shape
+                                 or residual.dtype != x.dtype):
+        raise ValueError("moe_experts: residual must match x")
+    if not _moe_on_device(x):
+        return _moe_compose(x, idx, w, w_gate, w_up, w_down, residual)
+    _require_ext("moe_experts")
+    idx = idx.int().contiguous()
+    if lists is None:
+        lists = _K.moe_align(idx, E)
+    return _K.moe_experts(
+        x.contiguous(), idx, w.float().contiguous(), lists,
+        w_gate.contiguous(), w_up.contiguous(), w_down.contiguous(),
+        None if residual is None else residual.contiguous())
+
+
+def moe_ffn(x, router_w, w_gate, w_up, w_down, top_k: int, residual=None):
+    """moe_experts over moe_route: the whole mixture-of-experts FFN of
+    x [M, H]. On the GPU the kernels serve every M inside a graph capture;
+    outside one, M >= MOE_COMPOSE_MIN_ROWS goes to the per-expert hipBLASLt
+    composition (it reads the routing on the host)."""
+    if w_gate.dim() != 3 or router_w.dim() != 2 \
+            or router_w.shape[0] != w_gate.shape[0]:
+        raise ValueError("moe_ffn: router_w [E, H] and w_gate [E, I, H]")
+    idx, w, lists = moe_route(x, router_w, top_k, with_lists=True)
+    if (lists is not None and x.shape[0] >= MOE_COMPOSE_MIN_ROWS
+            and not torch.cuda.is_current_stream_capturing()):
+        _moe_check(x, w_gate.shape[0], w_gate.shape[2], top_k, w_gate, w_up,
+                   w_down)
+        return _moe_compose(x, idx, w, w_gate, w_up, w_down, residual)
+    return moe_experts(x, idx, w, w_gate, w_up, w_down, residual, lists)
+
+
 class _SwigluMlpIn(torch.autograd.Function):
     """gate = x W_gate^T, up = x W_up^T. Backward: one grouped weight
     gradient launch (both share x). dx is the sum of the two dgrad GEMMs,
