@@ -27,6 +27,7 @@
 #include "hip/linear_w4_gemm.hip"
 #include "hip/lora.hip"
 #include "hip/moe.hip"
+#include "hip/moe_w4.hip"
 #include "hip/paged_attn.hip"
 #include "hip/paged_attn_prefill.hip"
 #include "hip/paged_attn_verify.hip"
@@ -876,9 +877,139 @@ at::Tensor moe_experts(at::Tensor x, at::Tensor idx, at::Tensor w,
   return y;
 }
 
+// moe_experts over MXFP4 expert weights (csrc/hip/moe_w4.hip): wq_gate,
+// wq_up uint8 [E, I, H/2] with scales [E, I, H/32], wq_down uint8
+// [E, H, I/2] with scales [E, H, I/32]. `split` is the number of K slices of
+// the down kernel (1, 2, 4 or 8; 0: the rule below); the result does not
+// depend on it. The workspaces (h [M*k, I] bf16, ws [S, M*k, H] fp32) have
+// sizes that depend on the shapes and `split` only: safe under capture.
+at::Tensor moe_experts_w4(at::Tensor x, at::Tensor idx, at::Tensor w,
+                          at::Tensor lists, at::Tensor wq_gate,
+                          at::Tensor s_gate, at::Tensor wq_up, at::Tensor s_up,
+                          at::Tensor wq_down, at::Tensor s_down,
+                          c10::optional<at::Tensor> residual, int64_t split) {
+  CHECK_IN(x); CHECK_IN(w); CHECK_IN(lists); CHECK_IN(wq_gate);
+  CHECK_IN(s_gate); CHECK_IN(wq_up); CHECK_IN(s_up); CHECK_IN(wq_down);
+  CHECK_IN(s_down);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16,
+              "moe_experts_w4: x must be bf16");
+  for (const at::Tensor* t :
+       {&wq_gate, &s_gate, &wq_up, &s_up, &wq_down, &s_down})
+    TORCH_CHECK(t->scalar_type() == at::kByte && t->dim() == 3,
+                "moe_experts_w4: expert weights and scales must be uint8 "
+                "[E, N, K/2] and [E, N, K/32]");
+  TORCH_CHECK(x.dim() == 2, "moe_experts_w4: x must be [M, H]");
+  const long long M = x.size(0), H = x.size(1);
+  const long long E = wq_gate.size(0), I = wq_gate.size(1);
+  moe_check_idx(idx, E, "moe_experts_w4");
+  const long long k = idx.size(1), P = M * k, G = moe_groups(P, E);
+  TORCH_CHECK(H > 0 && H % 128 == 0 && I > 0 && I % 128 == 0,
+              "moe_experts_w4: H and I must be multiples of 128");
+  auto is3 = [](const at::Tensor& t, long long a, long long b, long long c) {
+    return t.size(0) == a && t.size(1) == b && t.size(2) == c;
+  };
+  TORCH_CHECK(idx.size(0) == M && w.scalar_type() == at::kFloat &&
+                  w.dim() == 2 && w.size(0) == M && w.size(1) == k &&
+                  is3(wq_gate, E, I, H / 2) && is3(s_gate, E, I, H / 32) &&
+                  is3(wq_up, E, I, H / 2) && is3(s_up, E, I, H / 32) &&
+                  is3(wq_down, E, H, I / 2) && is3(s_down, E, H, I / 32),
+              "moe_experts_w4: shapes do not match");
+  TORCH_CHECK(lists.scalar_type() == at::kInt && lists.dim() == 1 &&
+                  lists.size(0) == 3 * G + P,
+              "moe_experts_w4: lists must come from moe_align for this idx");
+  TORCH_CHECK(aligned16(x) && aligned16(wq_gate) && aligned16(wq_up) &&
+                  aligned16(wq_down),
+              "moe_experts_w4: x and the expert weights must be 16-byte "
+              "aligned");
+  TORCH_CHECK((uintptr_t)s_gate.data_ptr() % 4 == 0 &&
+                  (uintptr_t)s_up.data_ptr() % 4 == 0 &&
+                  (uintptr_t)s_down.data_ptr() % 4 == 0,
+              "moe_experts_w4: the scales must be 4-byte aligned");
+  TORCH_CHECK(split == 0 || split == 1 || split == 2 || split == 4 ||
+              split == 8, "moe_experts_w4: split must be 0, 1, 2, 4 or 8");
+  const short* res = nullptr;
+  if (residual.has_value()) {
+    const at::Tensor& r = *residual;
+    CHECK_IN(r);
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 &&
+                    r.size(0) == M && r.size(1) == H && aligned16(r),
+                "moe_experts_w4: residual must be bf16 [M, H], 16-byte "
+                "aligned");
+    res = (const short*)r.data_ptr();
+  }
+  long long S = split;
+  if (S == 0) {
+    // The routing is not known here, so the live groups are taken as their
+    // most: min(P, E) experts hit plus P/64 full groups. The fewest slices
+    // that give every CU eight 128-channel blocks (forced S = 8 measured
+    // fastest or level at every M up to 64 on Mixtral's shapes, where a
+    // two-blocks-a-CU rule picked 2; PERFORMANCE.md, "MXFP4 expert
+    // weights"), while a slice keeps at least two 128-k steps and the fp32
+    // partials (4 bytes written and 4 read per element and slice) stay below
+    // the weight bytes of the experts hit: S*P*H*8 <= min(P, E)*H*I/2
+    const long long cus =
+        at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    const long long hit = std::min(P, E), live = hit + P / 64;
+    S = 1;
+    while (S < 8 && (H / 128) * live * S < 8 * cus && 4 * S <= I / 128 &&
+           32 * S * P <= hit * I)
+      S *= 2;
+  }
+  auto h = at::empty({P, I}, x.options());
+  auto ws = at::empty({S, P, H}, x.options().dtype(at::kFloat));
+  auto y = at::empty({M, H}, x.options());
+  const dim3 ggrid((unsigned)(I / 128), (unsigned)G);
+  const dim3 dgrid((unsigned)(H / 128), (unsigned)G, (unsigned)S);
+#define MOE_W4_DOWN(MT, CH, GPB)                                             \
+  hipLaunchKernelGGL((moe_down_w4_kernel<MT, CH, GPB>), dgrid, dim3(512), 0, \
+                     cur_stream(), (const short*)h.data_ptr(),               \
+                     (const unsigned char*)wq_down.data_ptr(),               \
+                     (const unsigned char*)s_down.data_ptr(),                \
+                     w.data_ptr<float>(), lists.data_ptr<int>(),             \
+                     ws.data_ptr<float>(), (int)P, (int)H, (int)I, (int)G)
+#define MOE_W4_LAUNCH(MT, CH)                                                \
+  hipLaunchKernelGGL((moe_gate_up_w4_kernel<MT, CH>), ggrid, dim3(512), 0,   \
+                     cur_stream(), (const short*)x.data_ptr(),               \
+                     (const unsigned char*)wq_gate.data_ptr(),               \
+                     (const unsigned char*)s_gate.data_ptr(),                \
+                     (const unsigned char*)wq_up.data_ptr(),                 \
+                     (const unsigned char*)s_up.data_ptr(),                  \
+                     lists.data_ptr<int>(), (short*)h.data_ptr(), (int)k,    \
+                     (int)H, (int)I, (int)G);                                \
+  switch (S) {                                                               \
+    case 1: MOE_W4_DOWN(MT, CH, 8); break;                                   \
+    case 2: MOE_W4_DOWN(MT, CH, 4); break;                                   \
+    case 4: MOE_W4_DOWN(MT, CH, 2); break;                                   \
+    default: MOE_W4_DOWN(MT, CH, 1); break;                                  \
+  }
+  // a group has at most min(64, P) pairs: the tiles a block stages
+  if (P <= 16) { MOE_W4_LAUNCH(1, 4); }
+  else if (P <= 32) { MOE_W4_LAUNCH(2, 2); }
+  else { MOE_W4_LAUNCH(4, 2); }
+#undef MOE_W4_LAUNCH
+#undef MOE_W4_DOWN
+  const long long total = M * (H / 4);
+  const dim3 cgrid((unsigned)((total + 255) / 256));
+#define MOE_W4_COMBINE(SS)                                                   \
+  hipLaunchKernelGGL(moe_w4_combine_kernel<SS>, cgrid, dim3(256), 0,         \
+                     cur_stream(), ws.data_ptr<float>(), w.data_ptr<float>(), \
+                     idx.data_ptr<int>(), res, (short*)y.data_ptr(), total,  \
+                     (int)k, (int)H, (int)E)
+  if (S == 1) {
+    hipLaunchKernelGGL(moe_combine_kernel, cgrid, dim3(256), 0, cur_stream(),
+                       ws.data_ptr<float>(), idx.data_ptr<int>(), res,
+                       (short*)y.data_ptr(), total, (int)k, (int)H, (int)E);
+  } else if (S == 2) { MOE_W4_COMBINE(2); }
+  else if (S == 4) { MOE_W4_COMBINE(4); }
+  else { MOE_W4_COMBINE(8); }
+#undef MOE_W4_COMBINE
+  HIP_CHECK_KERNEL();
+  return y;
+}
+
 // ---------------- paged-KV decode attention ----------------
 
-#define CHECK_I32(x)                                                   \
+#define CHECK_I32(x)                                                  \
   CHECK_IN(x);                                                          \
   TORCH_CHECK(x.scalar_type() == at::kInt, #x " must be int32")
 
@@ -1805,6 +1936,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_experts", &moe_experts, py::arg("x"), py::arg("idx"),
         py::arg("w"), py::arg("lists"), py::arg("w_gate"), py::arg("w_up"),
         py::arg("w_down"), py::arg("residual") = py::none());
+  m.def("moe_experts_w4", &moe_experts_w4, py::arg("x"), py::arg("idx"),
+        py::arg("w"), py::arg("lists"), py::arg("wq_gate"), py::arg("s_gate"),
+        py::arg("wq_up"), py::arg("s_up"), py::arg("wq_down"),
+        py::arg("s_down"), py::arg("residual") = py::none(),
+        py::arg("split") = 0);
   m.def("linear_w8_gemm", &linear_w8_gemm, py::arg("x"), py::arg("wq"),
         py::arg("scale"), py::arg("split") = 0, py::arg("rows_tile") = 0);
   m.def("sample", &sample, py::arg("logits"), py::arg("temperature"),

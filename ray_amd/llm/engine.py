@@ -22,6 +22,7 @@ from ray_amd.models.llama import (
     KVCache,
     LlamaModel,
     add_lora_slots,
+    quantize_experts_mxfp4,
     quantize_linears_fp8,
     quantize_linears_mxfp4,
 )
@@ -31,7 +32,8 @@ from ray_amd.models.llama import (
 class LLMConfig:
     # A key of models.llama.CONFIGS. "mixtral-8x7b" and "moe-tiny" are
     # mixture-of-experts models: ContinuousBatchingEngine with
-    # kv_cache="paged" only, expert weights in bf16 (ops.moe_ffn).
+    # kv_cache="paged" only, expert weights in bf16 or, with
+    # weight_dtype="mxfp4", in MXFP4 (ops.moe_ffn).
     model_id: str = "llama-tiny"
     max_seq_len: int = 512
     max_batch_size: int = 1
@@ -63,7 +65,10 @@ class LLMConfig:
     # the fp8 skinny-GEMM kernel. "mxfp4": they hold OCP MXFP4 instead, two
     # e2m1 elements per byte and one e8m0 scale byte per 32 of them, 17/32
     # byte per weight (ops.LinearW4), read by the W4A16 skinny-GEMM kernel.
-    # Activations stay in the model dtype.
+    # Activations stay in the model dtype. On a model with experts "mxfp4"
+    # also stores the expert weights as MXFP4 (the routed W4A16 expert
+    # kernels; the routers stay in the model dtype); "fp8" with such a model
+    # is not built and raises ValueError.
     weight_dtype: str = "auto"
     # ContinuousBatchingEngine with kv_cache="paged" only. max_loras > 0
     # gives every decoder-layer projection that many LoRA adapter slots of
@@ -378,13 +383,14 @@ class ContinuousBatchingEngine(_Sampling):
         if wq:
             if not self._paged:
                 raise ValueError(f"weight_dtype='{wq}' needs kv_cache='paged'")
-            if cfg.num_experts:
+            if cfg.num_experts and wq != "mxfp4":
                 raise ValueError(f"weight_dtype='{wq}' together with a model "
                                  "with experts is not built yet")
             if wq == "fp8":
                 quantize_linears_fp8(self.model)
             else:
                 quantize_linears_mxfp4(self.model)
+                quantize_experts_mxfp4(self.model)
         self._lora_rank = _lora_rank(config)
         # name -> {"slot": adapter slot, "root": its prefix-cache root}
         self._loras: dict = {}

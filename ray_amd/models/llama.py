@@ -104,6 +104,17 @@ def quantize_linears_mxfp4(model: "LlamaModel") -> "LlamaModel":
     return _quantize_linears(model, ops.LinearW4)
 
 
+def quantize_experts_mxfp4(model: "LlamaModel") -> "LlamaModel":
+    """Turn, in place, the expert weights of every MoEMLP block into MXFP4
+    buffers (MoEMLP.quantize_experts_mxfp4_): ops.moe_ffn then reads 17/32
+    byte per expert weight. The routers keep the model dtype; the model
+    serves inference only."""
+    for layer in model.layers:
+        if isinstance(layer.mlp, MoEMLP):
+            layer.mlp.quantize_experts_mxfp4_()
+    return model
+
+
 def _quantize_linears(model, cls):
     def swap(parent, names):
         for name in names:
@@ -281,12 +292,31 @@ class MoEMLP(nn.Module):
         for p in (self.w_gate, self.w_up, self.w_down):
             nn.init.normal_(p, std=0.02)
 
+    def quantize_experts_mxfp4_(self) -> "MoEMLP":
+        """Replace, in place, the three expert Parameters by MXFP4 buffers
+        (w_gate_q / w_gate_s, w_up_q / w_up_s, w_down_q / w_down_s: uint8
+        nibbles and e8m0 scales, 17/32 byte per weight), one expert at a
+        time, each bf16 Parameter freed once it is quantised. The router
+        keeps the model dtype. Inference only from then on."""
+        for name in ("w_gate", "w_up", "w_down"):
+            wq, s = ops.quantize_expert_weights_mxfp4(getattr(self, name).data)
+            delattr(self, name)
+            self.register_buffer(name + "_q", wq)
+            self.register_buffer(name + "_s", s)
+        return self
+
     def forward(self, x, residual=None):
         """The FFN of x [..., H]; `residual` (x's shape) is added before the
         one rounding to x's dtype."""
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])
         r2 = None if residual is None else residual.reshape(-1, shape[-1])
+        if hasattr(self, "w_gate_q"):
+            return ops.moe_ffn(
+                x2, self.router.weight, self.w_gate_q, self.w_up_q,
+                self.w_down_q, self.top_k, r2,
+                scales=(self.w_gate_s, self.w_up_s, self.w_down_s)
+            ).view(shape)
         return ops.moe_ffn(x2, self.router.weight, self.w_gate, self.w_up,
                            self.w_down, self.top_k, r2).view(shape)
 

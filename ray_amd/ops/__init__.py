@@ -373,6 +373,16 @@ def quantize_weight_mxfp4(w: torch.Tensor):
     return nib[..., 0] | (nib[..., 1] << 4), code.to(torch.uint8)
 
 
+def quantize_expert_weights_mxfp4(w: torch.Tensor):
+    """quantize_weight_mxfp4 of expert weights [E, N, K], expert by expert
+    (the fp64 temporaries stay at one expert's size): wq uint8 [E, N, K/2]
+    and scales uint8 [E, N, K/32], what ops.moe_experts takes with
+    `scales`."""
+    pairs = [quantize_weight_mxfp4(w[e]) for e in range(w.shape[0])]
+    return (torch.stack([p[0] for p in pairs]),
+            torch.stack([p[1] for p in pairs]))
+
+
 def dequantize_mxfp4(wq: torch.Tensor, scales: torch.Tensor,
                      dtype=torch.float32) -> torch.Tensor:
     """The weight [N, K] that (wq, scales) of quantize_weight_mxfp4 stand
@@ -724,6 +734,16 @@ MOE_MAX_ROWS = 65536
 # tools/moe_bench.py, PERFORMANCE.md "Mixture of experts"). A captured step
 # has at most 64 * (K + 1) rows and always runs the kernels.
 MOE_COMPOSE_MIN_ROWS = 512
+# The same threshold for MXFP4 expert weights (`scales` given): there the
+# composition also pays one dequantise pass per chosen expert and projection.
+# The kernels keep a row count only where their slowest repetition beat the
+# composition's fastest in tools/moe_bench.py --weights mxfp4 (µs, Mixtral
+# shapes, kernels' slowest / composition's fastest):
+#   M = 256:   670.6 / 2569.5      M = 512:  1122.5 / 2751.4
+#   M = 1024: 2392.8 / 3093.1      M = 1536: 3366.1 / 3382.6, and in another
+#   run 3587.2 / 3366.7 (lost);    M = 2048: 4484.2 / 3679.2 (lost)
+# so they keep every measured M up to 1024; 1536 is a tie that went both ways.
+MOE_W4_COMPOSE_MIN_ROWS = 1025
 
 
 def moe_route_ref(x, router_w, top_k: int, dtype=torch.float64):
@@ -740,12 +760,30 @@ def moe_route_ref(x, router_w, top_k: int, dtype=torch.float64):
     return idx.int(), w
 
 
-def moe_experts_ref(x, idx, w, w_gate, w_up, w_down, dtype=torch.float64):
+def _moe_expert_weights(e, dtype, w_gate, w_up, w_down, scales):
+    """Expert e's three weights in `dtype`; with `scales` they are MXFP4 and
+    only this expert is dequantised (exact; on the GPU in bf16 with grad off,
+    one dequant_mxfp4 kernel pass each)."""
+    if scales is None:
+        return w_gate[e].to(dtype), w_up[e].to(dtype), w_down[e].to(dtype)
+    if dtype == torch.bfloat16 and w_gate.is_cuda \
+            and not torch.is_grad_enabled():
+        _require_ext("dequant_mxfp4")
+        return tuple(_K.dequant_mxfp4(wq[e], s[e])
+                     for wq, s in zip((w_gate, w_up, w_down), scales))
+    return tuple(dequantize_mxfp4(wq[e], s[e], dtype)
+                 for wq, s in zip((w_gate, w_up, w_down), scales))
+
+
+def moe_experts_ref(x, idx, w, w_gate, w_up, w_down, dtype=torch.float64,
+                    scales=None):
     """y[m] = sum_j w[m, j] * (h_j @ w_down[e].T), h_j = silu(x[m] @
     w_gate[e].T) * (x[m] @ w_up[e].T), e = idx[m, j], one index_select ->
     matmul -> index_add_ per expert, in `dtype`. In float64 h is kept exact;
     otherwise h is rounded to bf16 once, like the kernels, and the result is
-    returned unrounded in `dtype`. Entries of idx outside 0..E-1 add nothing."""
+    returned unrounded in `dtype`. Entries of idx outside 0..E-1 add nothing.
+    With `scales` the weights are MXFP4 (see moe_experts), dequantised one
+    chosen expert at a time."""
     M, k = idx.shape
     E = w_gate.shape[0]
     xw = x.to(dtype)
@@ -757,11 +795,12 @@ def moe_experts_ref(x, idx, w, w_gate, w_up, w_down, dtype=torch.float64):
         if p.numel() == 0:
             continue
         xe = xw.index_select(0, p // k)
-        h = (torch.nn.functional.silu(xe @ w_gate[e].to(dtype).t())
-             * (xe @ w_up[e].to(dtype).t()))
+        wg, wu, wd = _moe_expert_weights(e, dtype, w_gate, w_up, w_down,
+                                         scales)
+        h = torch.nn.functional.silu(xe @ wg.t()) * (xe @ wu.t())
         if dtype != torch.float64:
             h = h.bfloat16().to(dtype)
-        pairs.index_add_(0, p, (h @ w_down[e].to(dtype).t())
+        pairs.index_add_(0, p, (h @ wd.t())
                          * w.reshape(-1)[p].to(dtype).unsqueeze(1))
     y = out[:, 0].clone()
     for j in range(1, k):  # slot order, as the combine kernel
@@ -769,7 +808,8 @@ def moe_experts_ref(x, idx, w, w_gate, w_up, w_down, dtype=torch.float64):
     return y
 
 
-def _moe_check(x, E, H, top_k, w_gate=None, w_up=None, w_down=None):
+def _moe_check(x, E, H, top_k, w_gate=None, w_up=None, w_down=None,
+               scales=None):
     if x.dim() != 2 or x.shape[1] != H:
         raise ValueError(f"moe: x must be [M, {H}], got {tuple(x.shape)}")
     if not 1 <= x.shape[0] <= MOE_MAX_ROWS:
@@ -786,6 +826,19 @@ def _moe_check(x, E, H, top_k, w_gate=None, w_up=None, w_down=None):
     I = w_gate.shape[1]
     if I % 128:
         raise ValueError(f"moe: expert width {I} is not a multiple of 128")
+    if scales is not None:
+        if len(scales) != 3:
+            raise ValueError("moe: scales must be (s_gate, s_up, s_down)")
+        want = ((E, I, H // 2), (E, I, H // 32), (E, I, H // 2),
+                (E, I, H // 32), (E, H, I // 2), (E, H, I // 32))
+        have = (w_gate, scales[0], w_up, scales[1], w_down, scales[2])
+        if any(t.dtype != torch.uint8 or tuple(t.shape) != s
+               for t, s in zip(have, want)):
+            raise ValueError(
+                "moe: with scales, w_gate and w_up must be uint8 [E, I, H/2] "
+                "with scales [E, I, H/32] and w_down uint8 [E, H, I/2] with "
+                "scales [E, H, I/32]")
+        return
     if (tuple(w_gate.shape) != (E, I, H) or tuple(w_up.shape) != (E, I, H)
             or tuple(w_down.shape) != (E, H, I)):
         raise ValueError("moe: w_gate and w_up must be [E, I, H] and w_down "
@@ -822,11 +875,13 @@ def moe_route(x, router_w, top_k: int, with_lists: bool = False):
     return (idx, w, lists) if with_lists else (idx, w)
 
 
-def _moe_compose(x, idx, w, w_gate, w_up, w_down, residual):
+def _moe_compose(x, idx, w, w_gate, w_up, w_down, residual, scales=None):
     """The torch composition. Off the GPU: moe_experts_ref in fp32 (fp64 for
     fp64 operands), the kernels' rounding points. bf16 on the GPU with grad
     off (the large-M dispatch of moe_ffn): three bf16 hipBLASLt GEMMs per
-    expert, which also round gate, up and the down product to bf16."""
+    expert, which also round gate, up and the down product to bf16. MXFP4
+    weights (`scales`) are dequantised to x's dtype one chosen expert at a
+    time, so a bf16 copy of all the experts never exists."""
     if _moe_on_device(x):
         M, k = idx.shape
         flat = idx.reshape(-1).long()
@@ -837,61 +892,89 @@ def _moe_compose(x, idx, w, w_gate, w_up, w_down, residual):
             if p.numel() == 0:
                 continue
             xe = x.index_select(0, p // k)
-            h = swiglu(xe @ w_gate[e].t(), xe @ w_up[e].t())
-            pairs.index_add_(0, p, (h @ w_down[e].t()).float()
+            wg, wu, wd = _moe_expert_weights(e, x.dtype, w_gate, w_up,
+                                             w_down, scales)
+            h = swiglu(xe @ wg.t(), xe @ wu.t())
+            pairs.index_add_(0, p, (h @ wd.t()).float()
                              * w.reshape(-1)[p].unsqueeze(1))
         y = pairs.view(M, k, -1).sum(dim=1)
     else:
         wide = torch.float64 if x.dtype == torch.float64 else torch.float32
-        y = moe_experts_ref(x, idx, w, w_gate, w_up, w_down, wide)
+        y = moe_experts_ref(x, idx, w, w_gate, w_up, w_down, wide, scales)
     if residual is not None:
         y = y + residual.to(y.dtype)
     return y.to(x.dtype)
 
 
-def moe_experts(x, idx, w, w_gate, w_up, w_down, residual=None, lists=None):
+def _moe_dims(w_gate, scales):
+    """(E, H) of expert weights [E, I, H], or of MXFP4 ones [E, I, H/2]."""
+    return w_gate.shape[0], w_gate.shape[2] * (1 if scales is None else 2)
+
+
+def moe_experts(x, idx, w, w_gate, w_up, w_down, residual=None, lists=None,
+                scales=None, split=0):
     """The routed expert FFNs: moe_experts_ref for given idx [M, k] and
     w [M, k], plus `residual` [M, H], rounded once to x's dtype. bf16 GPU
     operands with grad off run the HIP kernels over `lists` (moe_route's;
     built from idx on the device when None). Everything else runs the torch
-    composition with the same rounding points."""
+    composition with the same rounding points.
+
+    With `scales=(s_gate, s_up, s_down)` the expert weights are MXFP4, as
+    quantize_expert_weights_mxfp4 gives them: w_gate, w_up uint8 [E, I, H/2]
+    with scales uint8 [E, I, H/32], w_down uint8 [E, H, I/2] with scales
+    [E, H, I/32]. The kernels (csrc/hip/moe_w4.hip) read 17/32 byte per
+    weight and compute with exactly the values dequantize_mxfp4 returns;
+    `split` forces the K slices of the down kernel (1, 2, 4, 8; 0: by the
+    shapes), which the result does not depend on."""
     if w_gate.dim() != 3:
         raise ValueError("moe_experts: w_gate must be [E, I, H]")
-    E, _, H = w_gate.shape
+    E, H = _moe_dims(w_gate, scales)
     if idx.dim() != 2 or tuple(w.shape) != tuple(idx.shape) \
             or idx.shape[0] != x.shape[0]:
         raise ValueError("moe_experts: idx and w must be [M, k]")
-    _moe_check(x, E, H, idx.shape[1], w_gate, w_up, w_down)
+    _moe_check(x, E, H, idx.shape[1], w_gate, w_up, w_down, scales)
     if residual is not None and (residual.shape != x.shape
                                  or residual.dtype != x.dtype):
         raise ValueError("moe_experts: residual must match x")
     if not _moe_on_device(x):
-        return _moe_compose(x, idx, w, w_gate, w_up, w_down, residual)
+        return _moe_compose(x, idx, w, w_gate, w_up, w_down, residual, scales)
     _require_ext("moe_experts")
     idx = idx.int().contiguous()
     if lists is None:
         lists = _K.moe_align(idx, E)
+    res = None if residual is None else residual.contiguous()
+    if scales is not None:
+        return _K.moe_experts_w4(
+            x.contiguous(), idx, w.float().contiguous(), lists,
+            w_gate.contiguous(), scales[0].contiguous(), w_up.contiguous(),
+            scales[1].contiguous(), w_down.contiguous(),
+            scales[2].contiguous(), res, split)
     return _K.moe_experts(
         x.contiguous(), idx, w.float().contiguous(), lists,
-        w_gate.contiguous(), w_up.contiguous(), w_down.contiguous(),
-        None if residual is None else residual.contiguous())
+        w_gate.contiguous(), w_up.contiguous(), w_down.contiguous(), res)
 
 
-def moe_ffn(x, router_w, w_gate, w_up, w_down, top_k: int, residual=None):
+def moe_ffn(x, router_w, w_gate, w_up, w_down, top_k: int, residual=None,
+            scales=None, split=0):
     """moe_experts over moe_route: the whole mixture-of-experts FFN of
     x [M, H]. On the GPU the kernels serve every M inside a graph capture;
-    outside one, M >= MOE_COMPOSE_MIN_ROWS goes to the per-expert hipBLASLt
-    composition (it reads the routing on the host)."""
+    outside one, M >= MOE_COMPOSE_MIN_ROWS (MOE_W4_COMPOSE_MIN_ROWS for
+    MXFP4 weights, `scales` as in moe_experts) goes to the per-expert
+    hipBLASLt composition (it reads the routing on the host)."""
     if w_gate.dim() != 3 or router_w.dim() != 2 \
             or router_w.shape[0] != w_gate.shape[0]:
         raise ValueError("moe_ffn: router_w [E, H] and w_gate [E, I, H]")
     idx, w, lists = moe_route(x, router_w, top_k, with_lists=True)
-    if (lists is not None and x.shape[0] >= MOE_COMPOSE_MIN_ROWS
+    min_rows = (MOE_COMPOSE_MIN_ROWS if scales is None
+                else MOE_W4_COMPOSE_MIN_ROWS)
+    if (lists is not None and x.shape[0] >= min_rows
             and not torch.cuda.is_current_stream_capturing()):
-        _moe_check(x, w_gate.shape[0], w_gate.shape[2], top_k, w_gate, w_up,
-                   w_down)
-        return _moe_compose(x, idx, w, w_gate, w_up, w_down, residual)
-    return moe_experts(x, idx, w, w_gate, w_up, w_down, residual, lists)
+        _moe_check(x, *_moe_dims(w_gate, scales), top_k, w_gate, w_up,
+                   w_down, scales)
+        return _moe_compose(x, idx, w, w_gate, w_up, w_down, residual,
+                            scales)
+    return moe_experts(x, idx, w, w_gate, w_up, w_down, residual, lists,
+                       scales, split)
 
 
 class _SwigluMlpIn(torch.autograd.Function):
